@@ -1,12 +1,17 @@
 """Benchmark: DDPM train steps/sec of the conditional UNet (config/celebhq_text_image_cond.py, CelebHQ-256
 latents (B,4,32,32), per-GPU batch 32, text (B,77,512) + mask (B,18,512,512) conditioning) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     (N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
 
 One step = the reference's training step (train_ddpm_cond_celebhq_multi_gpu.py:299-378) on a synthetic
 batch already resident in HBM: cond-drop, noise/t draw, add_noise, forward, MSE, backward, RCCL
 all-reduce (N > 1), clip(1.0), Adam(1e-5), EMA(0.9999), bf16 weight repack. Prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line. --dump-outputs DIR also writes what the last
+timed step left its caller (DIR/<name>.npy, see dump_outputs). --full adds everything that takes runs of its own: the
+dominant-kernel roofline from extra profiled steps, the CPU baseline (unless --no-cpu-baseline), the eager-issue
+comparison of --workload sample and the exposed gradient-exchange tail (N > 1 / --force-reducer).
 """
 import argparse
 import json
@@ -157,6 +162,55 @@ def synthetic_batch(B, device, seed):
 def dit_config():
     from tests.golden.configs import dit12l_config
     return dit12l_config()
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs: budget of all arrays' data together (64 MB with room for the .npy headers)
+DUMP_SEED = 20240229
+
+
+def seeded_sample(flat, n):
+    """`flat` (1-D) itself when it has at most n elements, else its values at n fixed positions: sorted draws of a
+    CPU generator seeded by DUMP_SEED and the length alone, so two builds sample the same elements."""
+    if flat.numel() <= n:
+        return flat
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED + flat.numel() % 1000003)
+    idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as dirname/<name>.npy, float32 (integer tensors:
+    float64), flattened. Each array gets an equal share of DUMP_BYTES; one that fits its share is written whole, a
+    larger one as seeded_sample() of its share. Returns {name: [elements written, elements of the output]}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    written = {}
+    for name, v in arrays.items():
+        v = v.detach().reshape(-1)
+        dt = torch.float32 if v.is_floating_point() else torch.float64
+        s = seeded_sample(v, share // (4 if dt == torch.float32 else 8))
+        np.save(os.path.join(dirname, name + ".npy"), s.to(dt).cpu().numpy())
+        written[name] = [s.numel(), v.numel()]
+    return written
+
+
+def trainer_outputs(trainer):
+    """What DDPMTrainer.step() leaves its caller: the state vector it returns (gradient norm, clip coefficient, loss
+    scale, growth count, step count, skip flag, loss, DP flag) and, behind state_dict() / ema_state_dict() and the
+    flat store, the updated parameters, EMA copy, Adam moments and the step's gradients -- each as one vector of the
+    tensors in torch order, concatenated by sorted key (independent of the store's own layout)."""
+    trainer.sync_optimizer()
+    st = trainer.store
+    keys = sorted(st.order)
+
+    def cat(get):
+        return torch.cat([trainer._export(get(k).detach()).reshape(-1) for k in keys])
+    out = {"state": trainer.state, "params": cat(lambda k: st.p[k]), "grads": cat(lambda k: st.g[k]),
+           "adam_m": cat(lambda k: st.view(trainer.m, k)), "adam_v": cat(lambda k: st.view(trainer.v, k))}
+    if trainer.ema is not None:
+        out["ema"] = cat(lambda k: st.view(trainer.ema, k))
+    return out
 
 
 def cpu_model():
@@ -372,8 +426,9 @@ def main_vqvae(args, wl, world, rank, device):
 
     def step():
         zq, loss, idx = eng.encode(x)
-        eng.decode(zq)
+        return zq, loss, idx, eng.decode(zq)
 
+    last = None
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -381,7 +436,7 @@ def main_vqvae(args, wl, world, rank, device):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -391,14 +446,18 @@ def main_vqvae(args, wl, world, rank, device):
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = e.item()
     sps = args.steps / elapsed
-    from sdmi import kernels as K
-    PROF_STEPS = 3
-    K.PROFILE = []
-    for _ in range(PROF_STEPS):
-        step()
-    torch.cuda.synchronize()
-    prof, K.PROFILE = K.PROFILE, None
-    roof = gemm_roofline(prof, PROF_STEPS, args.workload)
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, dict(zip(("zq", "quantize_loss", "indices", "decoded"), last)))
+    roof = None
+    if args.full:
+        from sdmi import kernels as K
+        PROF_STEPS = 3
+        K.PROFILE = []
+        for _ in range(PROF_STEPS):
+            step()
+        torch.cuda.synchronize()
+        prof, K.PROFILE = K.PROFILE, None
+        roof = gemm_roofline(prof, PROF_STEPS, args.workload)
     result = {"metric": wl["metric"], "value": sps * world, "unit": "steps/s", "n_gpus": world, "steps": args.steps,
               "warmup": args.warmup, "ms_per_step": 1000.0 / sps, "higher_is_better": True, "scaling": "weak",
               "vs_baseline": None, "dtype": "bf16", "data": "synthetic 256x256 images, random-init weights",
@@ -407,7 +466,7 @@ def main_vqvae(args, wl, world, rank, device):
                          "parallelism": f"replicas{world}"},
               "images_per_s": sps * B * world, "model_flops_utilization": wl["flop"] * sps / PEAK_BF16,
               "roofline": roof}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_vqvae(cfg)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -463,15 +522,23 @@ def main_vqvae_train(args, wl, world, rank, device):
         elapsed = e.item()
     sps = args.steps / elapsed
     losses = tr.losses()
-    # dominant-kernel roofline: eager steps with the GEMM launches timed by HIP events on their own streams
-    from sdmi import kernels as K
-    PROF_STEPS = 3
-    K.PROFILE = []
-    for _ in range(PROF_STEPS):
-        tr.step(x)
-    torch.cuda.synchronize()
-    prof, K.PROFILE = K.PROFILE, None
-    roof = gemm_roofline(prof, PROF_STEPS, args.workload)
+    if args.dump_outputs and rank == 0:
+        sd = tr.state_dict()
+        dump_outputs(args.dump_outputs, {
+            "state": tr.state, "reconstruction": tr.reconstruction(),
+            "losses": torch.tensor([float(losses[k]) for k in sorted(losses)], dtype=torch.float32),
+            "params": torch.cat([sd[k].detach().reshape(-1) for k in sorted(sd)])})
+    roof = None
+    if args.full:
+        # dominant-kernel roofline: eager steps with the GEMM launches timed by HIP events on their own streams
+        from sdmi import kernels as K
+        PROF_STEPS = 3
+        K.PROFILE = []
+        for _ in range(PROF_STEPS):
+            tr.step(x)
+        torch.cuda.synchronize()
+        prof, K.PROFILE = K.PROFILE, None
+        roof = gemm_roofline(prof, PROF_STEPS, args.workload)
     result = {"metric": wl["metric"], "value": sps * world, "unit": "steps/s", "n_gpus": world, "steps": args.steps,
               "warmup": args.warmup, "ms_per_step": 1000.0 / sps, "higher_is_better": True, "scaling": "weak",
               "vs_baseline": None, "dtype": "bf16", "data": "synthetic 256x256 images, random-init weights",
@@ -481,7 +548,7 @@ def main_vqvae_train(args, wl, world, rank, device):
                          "parallelism": f"dp{world}", "issue": args.issue},
               "images_per_s": sps * B * world, "model_flops_utilization": wl["flop"] * sps / PEAK_BF16,
               "last_losses": losses, "roofline": roof}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_vqvae_train(cfg)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -512,15 +579,15 @@ def main_sample(args, wl, world, rank, device):
     else:
         loop = DDPMSampleLoop(model, sched, (B, 4, 32, 32), cond_input=cond, seed=rank)
         run = lambda n, cap: loop.run(xT, steps=n, captured=cap)  # noqa: E731
-    res = {}
-    for mode in ("captured", "eager"):
+    res = {"eager": None}
+    for mode in ("captured", "eager") if args.full else ("captured",):  # the eager-issue comparison: --full only
         cap = mode == "captured"
         run(args.warmup + 1, cap)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         t0 = time.perf_counter()
-        run(args.steps, cap)
+        out = run(args.steps, cap)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -530,23 +597,28 @@ def main_sample(args, wl, world, rank, device):
             dist.all_reduce(e, op=dist.ReduceOp.MAX)
             el = e.item()
         res[mode] = args.steps / el
+        if cap and args.dump_outputs and rank == 0:  # DDPM: (x after the steps, its predicted x0); DDIM: x
+            out = out if isinstance(out, tuple) else (out,)
+            dump_outputs(args.dump_outputs, dict(zip(("xt", "x0_pred"), out)))
     sps = res["captured"]
-    # roofline of the step's GEMM launches (every implicit-GEMM conv and linear of the forward, HIP events on their
-    # stream, one eager reverse step): at B = 1 the grids are small and each launch is latency-bound
-    from sdmi import kernels as K
-    K.PROFILE = []
-    loop._refresh()
-    loop._step()  # one eager reverse step (model forward + the sampler's update kernel)
-    torch.cuda.synchronize()
-    prof, K.PROFILE = K.PROFILE, None
-    gfl = sum(p[1] for p in prof if p[0].startswith("gemm"))
-    gms = sum(p[2].elapsed_time(p[3]) for p in prof if p[0].startswith("gemm"))
-    ngemm = sum(1 for p in prof if p[0].startswith("gemm"))
-    roof = {"bound": "mfma", "kernel": "sdmi gemm (all implicit-GEMM conv / linear launches of one reverse step)",
-            "achieved": gfl / (gms * 1e-3) / 1e12 if gms else None, "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
-            "frac": gfl / (gms * 1e-3) / PEAK_BF16 if gms else None, "traffic": None, "launches": ngemm,
-            "avg_launch_us": gms * 1e3 / max(1, ngemm), "flop_per_launch": gfl / max(1, ngemm),
-            "gemm_ms_per_step": gms}
+    roof = None
+    if args.full:
+        # roofline of the step's GEMM launches (every implicit-GEMM conv and linear of the forward, HIP events on
+        # their stream, one eager reverse step): at B = 1 the grids are small and each launch is latency-bound
+        from sdmi import kernels as K
+        K.PROFILE = []
+        loop._refresh()
+        loop._step()  # one eager reverse step (model forward + the sampler's update kernel)
+        torch.cuda.synchronize()
+        prof, K.PROFILE = K.PROFILE, None
+        gfl = sum(p[1] for p in prof if p[0].startswith("gemm"))
+        gms = sum(p[2].elapsed_time(p[3]) for p in prof if p[0].startswith("gemm"))
+        ngemm = sum(1 for p in prof if p[0].startswith("gemm"))
+        roof = {"bound": "mfma", "kernel": "sdmi gemm (all implicit-GEMM conv / linear launches of one reverse step)",
+                "achieved": gfl / (gms * 1e-3) / 1e12 if gms else None, "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
+                "frac": gfl / (gms * 1e-3) / PEAK_BF16 if gms else None, "traffic": None, "launches": ngemm,
+                "avg_launch_us": gms * 1e3 / max(1, ngemm), "flop_per_launch": gfl / max(1, ngemm),
+                "gemm_ms_per_step": gms}
     result = {"metric": wl["metric"].replace("DDPM", "DDIM") if args.sampler == "ddim" else wl["metric"], "value": sps * world, "unit": "steps/s", "n_gpus": world, "steps": args.steps,
               "warmup": args.warmup, "ms_per_step": 1000.0 / sps, "higher_is_better": True, "scaling": "weak",
               "vs_baseline": None, "dtype": "bf16", "data": "synthetic latents / text / masks, random-init weights",
@@ -555,7 +627,7 @@ def main_sample(args, wl, world, rank, device):
                          "sampler": args.sampler, "issue": loop.issue,
                          "model": "cond-UNet 118.5M", "samples_per_gpu": B, "latent": [4, 32, 32],
                          "parallelism": f"replicas{world}"},
-              "eager_steps_per_s": res["eager"], "captured_speedup": sps / res["eager"],
+              "eager_steps_per_s": res["eager"], "captured_speedup": sps / res["eager"] if res["eager"] else None,
               "model_flops_utilization": wl["flop"] * B * sps / PEAK_BF16, "roofline": roof}
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -590,7 +662,14 @@ def main():
     ap.add_argument("--sample-batch", type=int, default=1, help="samples per GPU of --workload sample (reference: 1)")
     ap.add_argument("--sampler", default="ddpm", choices=("ddpm", "ddim"),
                     help="--workload sample: DDPM (T steps of sample_prev_timestep) or DDIM (--steps pairs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the dominant-kernel roofline "
+                         "(extra profiled steps), the CPU baseline, the eager-issue comparison of --workload sample and "
+                         "the exposed gradient-exchange tail (N > 1 / --force-reducer)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB "
+                         "in all: larger outputs as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--workload", default="cond-unet", choices=sorted(WORKLOADS),
                     help="cond-unet (the headline metric, default), uncond-unet (celebhq.yaml), dit (DiT-12L training "
                          "step), vqvae (encode + decode), vqvae-train (VQVAE generator step) or sample (captured DDPM sampling loop)")
@@ -727,14 +806,16 @@ def main():
         elapsed = e.item()
     steps_per_s = args.steps / elapsed
     state = trainer.state.tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer_outputs(trainer))
 
-    # dominant-kernel roofline: the implicit-GEMM conv/linear launches of PROF_STEPS extra (untimed) steps, timed
-    # with HIP events on the stream they run on (averaged over the steps: one step's concurrency noise is ~10 %)
+    # --full: dominant-kernel roofline: the implicit-GEMM conv/linear launches of PROF_STEPS extra (untimed) steps,
+    # timed with HIP events on the stream they run on (averaged over the steps: one step's concurrency noise is ~10 %)
     roof = None
-    if args.profile_gemm:
+    tails = []
+    if args.full and args.profile_gemm:
         PROF_STEPS = 3
         K.PROFILE = []
-        tails = []
         if trainer.reducer is not None:
             trainer.measure_exchange_tail()
         for _ in range(PROF_STEPS):
@@ -779,13 +860,13 @@ def main():
     if world > 1 or forced:
         result["collectives"] = collectives
         result["grad_wire"] = trainer.grad_wire
-        if args.profile_gemm and tails:
+        if tails:
             # exposed gradient exchange: compute-stream time from the end of the backward (all gradients final) to the
             # last bucket's all-reduce waited for, eager profiled steps (HIP events), max over ranks
             tail = torch.tensor([sum(tails) / len(tails)], device=device, dtype=torch.float64)
             dist.all_reduce(tail, op=dist.ReduceOp.MAX)
             result["exchange_tail_ms"] = tail.item()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_dit(cfg) if is_dit else cpu_baseline(cfg, uncond=is_uncond)
     if rank == 0:
         print(json.dumps(result), flush=True)

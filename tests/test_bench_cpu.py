@@ -23,6 +23,25 @@ def test_kernel_glob_matches_its_instantiations_only():
     assert bench.kernel_name("gemm_a0b0", "variant=0 tile_n=128") == "gemm_kernel<0, 0, *>"
 
 
+def test_dump_outputs_writes_whole_small_arrays_and_a_fixed_sample_of_large_ones(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 400)  # three arrays: 100 float32 / 50 float64 elements each
+    big = torch.arange(1000, dtype=torch.float32) * 0.5
+    arrays = {"small": torch.arange(12, dtype=torch.bfloat16).reshape(3, 4), "big": big,
+              "ints": torch.arange(7, dtype=torch.int64)}
+    written = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert written == {"small": [12, 12], "big": [100, 1000], "ints": [7, 7]}
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert a["small"].dtype == np.float32 and a["big"].dtype == np.float32 and a["ints"].dtype == np.float64
+    assert a["small"].tolist() == list(range(12)) and a["ints"].tolist() == list(range(7))
+    # the sample: 100 elements of the array itself, in order, and the same ones in every run
+    assert a["big"].shape == (100,) and np.all(np.diff(a["big"]) >= 0) and set(a["big"]) <= set(big.tolist())
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(v.nbytes for v in a.values()) <= 3 * 400
+
+
 @pytest.mark.parametrize("workload", ["cond-unet", "dit", "uncond-unet"])
 def test_roofline_evidence_is_the_newest_and_digest_tagged(workload):
     import sys
