@@ -1648,7 +1648,9 @@ int pick_variant(const sdmi_gemm_desc* d) {
   int v = gemm_variant();
   if (v < 0 && d->variant_hint >= 1 && d->variant_hint <= 11) v = d->variant_hint == 1 ? 0 : d->variant_hint;
   if (v < 0) v = 2;  // (col-major A with [n][k] B has no DMA instantiation: register staging below)
-  if (has_reductions(d) && (v == 3 || !dma_reductions_ok(d))) v = v == 3 ? 2 : 0;
+  // (group sums the DMA kernels cannot form go to register staging whatever was requested, 3 included)
+  if (has_reductions(d) && !dma_reductions_ok(d)) v = 0;
+  else if (has_reductions(d) && v == 3) v = 2;
   if (has_reductions(d) && v != 0 && d->a_mode != SDMI_A_COLMAJOR) v = 0;
   // the DMA path needs a tile-uniform second source (k_split % BK == 0)
   if (d->a_mode == SDMI_A_CONV && d->a2 && d->k_split % BK) v = 0;
