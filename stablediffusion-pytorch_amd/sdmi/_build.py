@@ -1,7 +1,9 @@
 """Builds libsdmi.so (all HIP kernels + the C ABI of include/sdmi.h) in-tree for gfx950.
 
 The shared library is compiled with plain hipcc (no torch headers): the boundary is a C ABI and
-Python binds it with ctypes (sdmi/_lib.py)."""
+Python binds it with ctypes (sdmi/_lib.py). Every csrc/*.hip is one translation unit, compiled in parallel; the
+GEMM family is several of them (gemm.hip host side, gemm_staged / gemm_dma_* / gemm_reduce kernels) sharing the
+gemm_*.h headers."""
 import os
 import subprocess
 import sys
@@ -12,15 +14,21 @@ CSRC = os.path.join(PKG, "csrc")
 REPO = os.path.dirname(PKG)
 LIB = os.path.join(HERE, "libsdmi.so")
 ARCH = "gfx950"
-# per-source extra flags. attention.hip: softmax maxima are taken straight from MFMA accumulators; in the default
+# per-source extra flags, by file-name prefix. attention.hip: softmax maxima are taken straight from MFMA accumulators; in the default
 # IEEE mode every fmaxf input would first be quieted by a canonicalising v_max_f32 (one extra VALU op per score).
 # The kernels never produce or consume NaNs (masked scores are -inf), so IEEE mode is switched off there.
 # -fno-slp-vectorize: the softmax VALU is written as scalar f32 ops; SLP would re-pack adjacent ones into
 # v_pk_{fma,mul,add}_f32, which beside MFMAs cost about three times two scalar ops (MI355X guide, 'price of one
 # filler beside MFMAs').
 EXTRA_FLAGS = {"attention.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee", "-fno-slp-vectorize"],
-               # gemm.hip: the VALU bias row sums of the weight-gradient mainloop run beside the MFMAs (same reason)
-               "gemm.hip": ["-fno-slp-vectorize"]}
+               # gemm*.hip (the host side gemm.hip and every source holding GEMM kernels: gemm_staged, gemm_dma_*,
+               # gemm_reduce): the VALU bias row sums of the weight-gradient mainloop run beside the MFMAs (same reason)
+               "gemm": ["-fno-slp-vectorize"]}
+
+
+def extra_flags(src):
+    name = os.path.basename(src)
+    return [f for prefix, flags in EXTRA_FLAGS.items() if name.startswith(prefix) for f in flags]
 
 
 def sources():
@@ -48,7 +56,7 @@ def build(force=False, verbose=False, out=None, defines=()):
         obj = os.path.join("/tmp", "sdmi_" + os.path.basename(src) + f".{os.getpid()}.o")
         cmd = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj,
                "-I", os.path.join(REPO, "include"), "-Rpass-analysis=kernel-resource-usage"]
-        cmd += EXTRA_FLAGS.get(os.path.basename(src), [])
+        cmd += extra_flags(src)
         cmd += [f"-D{d}" for d in defines]
         procs.append((subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT), src, cmd))
         objs.append(obj)

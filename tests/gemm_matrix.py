@@ -1,8 +1,9 @@
-"""The declared test matrix of sdmi_gemm (csrc/gemm.hip) and the helpers its exact tests share.
+"""The declared test matrix of sdmi_gemm (csrc/gemm.hip and the gemm_* sources it launches) and the helpers its exact
+tests share.
 
 ROWS is data: one row per kernel instantiation, `(a_mode, b_mode, requested variant, expected variant, expected
 tile_n, extras)`. The expected variant and column tile are written by hand from the rules stated in the comments of
-pick_variant / pick_tbn -- they are the independent statement of what should run, never computed by calling the
+pick_variant / pick_tbn and the variant table (csrc/gemm_variants.h) -- they are the independent statement of what should run, never computed by calling the
 library -- and tests/test_gemm_variants_gpu.py asserts after every launch that the library's own log agrees.
 tests/test_gemm_matrix_cpu.py asserts that every (mode, variant, split, second source, permute, conv kernel) class of
 sdmi/tuned_gemm.json has a row here.
