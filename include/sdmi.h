@@ -336,6 +336,18 @@ int sdmi_pointwise_in(const float* z, int B, int C, int HW, const float* w, cons
  *                   alpha_prev = abar[tp[i]] (DDIMSampler.forward's time_steps / time_steps_prev, :231-242); advance:
  *                   afterwards *idx -= 1 and *t_dev = ts[*idx] (the model's timestep) -- a capturable DDIM loop.
  *  sdmi_affine_step: DDPMSampler.sample_one_step (:111-124): out = (c1 x - c2 eps) + sqrt(var) z (z NULL: + 0).
+ * Classifier-free guidance (tools/sample_ddpm_text_cond.py:62-64, the generator scripts' _GuidedWrapper): a guided
+ * step runs ONE forward of batch 2B, rows [0, B) conditional and [B, 2B) unconditional, and combines the halves.
+ *  sdmi_cfg_combine : out = eps_uncond + scale * (eps_cond - eps_uncond) over n fp32 elements; sub, mul and add are
+ *                   rounded separately (no contraction), bit-identical to the torch expression. out may alias
+ *                   either input. Returns -1 on a NULL pointer or n <= 0, before any launch.
+ *  sdmi_cfg_combine_nhwc : the same combine fused with sdmi_nhwc_to_nchw's layout change (same parameter
+ *                   conventions): pred holds 2*B*HW rows of stride ld (fp32, or bf16 when src_f32 == 0), rows
+ *                   [0, B*HW) conditional and the rest unconditional; dst is (B, C, HW) NCHW fp32; columns C..ld-1
+ *                   are never read. Returns -1 on a NULL pointer, a non-positive size or ld < C.
+ *  sdmi_ddpm_prev_dup / sdmi_ddim_prev_dev_dup : sdmi_ddpm_prev / sdmi_ddim_prev_dev with a second output pointer
+ *                   (prev2 / out2, NULL: none) that receives the same x_{t-1}: the unconditional half of the next
+ *                   guided step's doubled input, written by the step itself instead of a copy launch.
  * ------------------------------------------------------------------------------------------- */
 int sdmi_ddpm_prev(const float* xt, const float* eps, const float* z, long long n, long long* t_dev, const float* betas,
                    const float* alphas, const float* abar, const float* s1m, float* prev, float* x0, int decrement_t,
@@ -347,6 +359,16 @@ int sdmi_ddim_prev_dev(const float* xt, const float* eps, const float* noise, lo
                        int advance, sdmi_stream_t stream);
 int sdmi_affine_step(const float* x, const float* eps, const float* z, long long n, float c1, float c2, float var,
                      float* out, sdmi_stream_t stream);
+int sdmi_cfg_combine(const float* eps_cond, const float* eps_uncond, long long n, float scale, float* out,
+                     sdmi_stream_t stream);
+int sdmi_cfg_combine_nhwc(const void* pred, int src_f32, int ld, int B, int C, int HW, float scale, float* dst,
+                          sdmi_stream_t stream);
+int sdmi_ddpm_prev_dup(const float* xt, const float* eps, const float* z, long long n, long long* t_dev,
+                       const float* betas, const float* alphas, const float* abar, const float* s1m, float* prev,
+                       float* prev2, float* x0, int decrement_t, sdmi_stream_t stream);
+int sdmi_ddim_prev_dev_dup(const float* xt, const float* eps, const float* noise, long long n, const long long* ts,
+                           const long long* tp, long long* idx, long long* t_dev, const float* abar, float eta,
+                           float* out, float* out2, int advance, sdmi_stream_t stream);
 
 /* Device standard-normal noise (captured sampling loops): out[i] ~ N(0,1), Philox4x32-10(seed, i / 4, *offset_dev)
  * + Box-Muller; advance != 0 increments *offset_dev after the draw (the next replay draws fresh noise). Replaces

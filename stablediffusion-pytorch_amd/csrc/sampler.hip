@@ -12,6 +12,12 @@
 //  ddim_prev_dev : the same step with (t, t_prev) read from device tables through a device step index, which a
 //              follow-up launch decrements (and the model's timestep scalar with it): a captured DDIM loop.
 //  affine    : DDPMSampler.sample_one_step (:111-124): (c1 x - c2 eps) + sqrt(var) z with host table scalars.
+//  cfg_combine : classifier-free guidance (tools/sample_ddpm_text_cond.py:62-64, the generators' _GuidedWrapper):
+//              eps = eps_uncond + scale (eps_cond - eps_uncond) on the two halves of ONE doubled-batch forward
+//              [cond | uncond]; sub / mul / add rounded separately, bit-identical to the torch expression. The
+//              nhwc form reads the UNet's NHWC prediction and writes NCHW (it replaces nhwc_to_nchw in a guided
+//              step); ddpm_prev / ddim_prev_dev take a second output pointer (the *_dup entry points) so x_{t-1}
+//              reaches both halves of the next step's doubled input without a copy launch.
 #include "common.h"
 #include "../../include/sdmi.h"
 #include <algorithm>
@@ -28,7 +34,7 @@ __device__ __forceinline__ float sqrt_ieee(float a) { return (float)__dsqrt_rn((
 
 __global__ void ddpm_prev_kernel(const float* xt, const float* eps, const float* z, long long n, const long long* tp,
                                  const float* betas, const float* alphas, const float* abar, const float* s1m,
-                                 float* prev, float* x0out) {
+                                 float* prev, float* prev2, float* x0out) {
 #pragma clang fp contract(off)
   const long long t = *tp;
   const float sq_abar = sqrt_ieee(abar[t]);
@@ -45,7 +51,9 @@ __global__ void ddpm_prev_kernel(const float* xt, const float* eps, const float*
     float mean = sub_ieee(x, div_ieee(mul_ieee(beta, e), s1));
     mean = div_ieee(mean, sq_alpha);
     if (x0out) x0out[i] = x0;
-    prev[i] = t > 0 ? add_ieee(mean, mul_ieee(sigma, z[i])) : mean;
+    const float p = t > 0 ? add_ieee(mean, mul_ieee(sigma, z[i])) : mean;
+    prev[i] = p;
+    if (prev2) prev2[i] = p;
   }
 }
 
@@ -75,7 +83,7 @@ __global__ void ddim_prev_kernel(const float* xt, const float* eps, const float*
 // step is bit-identical to the eager one given the same noise
 __global__ void ddim_prev_dev_kernel(const float* xt, const float* eps, const float* noise, long long n,
                                      const long long* ts, const long long* tp, const long long* idx, const float* abar,
-                                     float eta, float* out) {
+                                     float eta, float* out, float* out2) {
 #pragma clang fp contract(off)
   const long long i = *idx;
   const float at = abar[ts[i]], ap = abar[tp[i]];
@@ -86,7 +94,9 @@ __global__ void ddim_prev_dev_kernel(const float* xt, const float* eps, const fl
                              sqrt_ieee(div_ieee(mul_ieee(ap, sub_ieee(1.0f, at)), at)));
   for (long long j = (long long)blockIdx.x * NT + threadIdx.x; j < n; j += (long long)gridDim.x * NT) {
     float v = add_ieee(mul_ieee(c1, xt[j]), mul_ieee(c2, eps[j]));
-    out[j] = add_ieee(v, mul_ieee(sigma, noise ? noise[j] : 0.0f));
+    v = add_ieee(v, mul_ieee(sigma, noise ? noise[j] : 0.0f));
+    out[j] = v;
+    if (out2) out2[j] = v;
   }
 }
 
@@ -110,22 +120,57 @@ __global__ void affine_kernel(const float* x, const float* eps, const float* z, 
   }
 }
 
+// classifier-free guidance: out = u + scale * (c - u), each operation rounded on its own (torch evaluates the
+// reference's expression as three fp32 ops). Elementwise, so out may alias either input.
+__global__ void cfg_combine_kernel(const float* c, const float* u, long long n, float scale, float* out) {
+#pragma clang fp contract(off)
+  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
+    const float uv = u[i];
+    out[i] = add_ieee(uv, mul_ieee(scale, sub_ieee(c[i], uv)));
+  }
+}
+
+// the same combine read from an NHWC prediction of 2*B*HW rows (fp32 or bf16, row stride ld; rows [0, B*HW)
+// conditional, the rest unconditional) and written as (B, C, HW) NCHW fp32: nhwc_to_nchw's indexing, columns
+// C..ld-1 never read
+__global__ void cfg_combine_nhwc_kernel(const void* pred, int src_f32, int ld, int B, int C, int HW, float scale,
+                                        float* dst) {
+#pragma clang fp contract(off)
+  const long long total = (long long)B * C * HW, half = (long long)B * HW * ld;
+  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
+    const int p = (int)(i % HW);
+    const long long bc = i / HW;
+    const int c = (int)(bc % C);
+    const int b = (int)(bc / C);
+    const long long s = ((long long)b * HW + p) * ld + c;
+    const float cv = src_f32 ? ((const float*)pred)[s] : bf2f(((const bf16_t*)pred)[s]);
+    const float uv = src_f32 ? ((const float*)pred)[s + half] : bf2f(((const bf16_t*)pred)[s + half]);
+    dst[i] = add_ieee(uv, mul_ieee(scale, sub_ieee(cv, uv)));
+  }
+}
+
 int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + NT - 1) / NT, 4096)); }
 
 }  // namespace
 
-extern "C" int sdmi_ddpm_prev(const float* xt, const float* eps, const float* z, long long n, long long* t_dev,
-                              const float* betas, const float* alphas, const float* abar, const float* s1m,
-                              float* prev, float* x0, int decrement_t, sdmi_stream_t stream) {
+extern "C" int sdmi_ddpm_prev_dup(const float* xt, const float* eps, const float* z, long long n, long long* t_dev,
+                                  const float* betas, const float* alphas, const float* abar, const float* s1m,
+                                  float* prev, float* prev2, float* x0, int decrement_t, sdmi_stream_t stream) {
   if (!xt || !eps || !t_dev || !betas || !alphas || !abar || !s1m || !prev || n <= 0) return -1;
   sdmi_rt::launch(ddpm_prev_kernel, dim3(grid_for(n)), dim3(NT), 0, (hipStream_t)stream, xt, eps, z, n, t_dev,
-                     betas, alphas, abar, s1m, prev, x0);
+                     betas, alphas, abar, s1m, prev, prev2, x0);
   SDMI_CHECK_LAUNCH();
   if (decrement_t) {
     sdmi_rt::launch(dec_t_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t_dev);
     SDMI_CHECK_LAUNCH();
   }
   return 0;
+}
+
+extern "C" int sdmi_ddpm_prev(const float* xt, const float* eps, const float* z, long long n, long long* t_dev,
+                              const float* betas, const float* alphas, const float* abar, const float* s1m,
+                              float* prev, float* x0, int decrement_t, sdmi_stream_t stream) {
+  return sdmi_ddpm_prev_dup(xt, eps, z, n, t_dev, betas, alphas, abar, s1m, prev, nullptr, x0, decrement_t, stream);
 }
 
 extern "C" int sdmi_ddim_prev(const float* xt, const float* eps, const float* noise, long long n, float alpha_t,
@@ -137,17 +182,42 @@ extern "C" int sdmi_ddim_prev(const float* xt, const float* eps, const float* no
   return 0;
 }
 
-extern "C" int sdmi_ddim_prev_dev(const float* xt, const float* eps, const float* noise, long long n,
-                                  const long long* ts, const long long* tp, long long* idx, long long* t_dev,
-                                  const float* abar, float eta, float* out, int advance, sdmi_stream_t stream) {
+extern "C" int sdmi_ddim_prev_dev_dup(const float* xt, const float* eps, const float* noise, long long n,
+                                      const long long* ts, const long long* tp, long long* idx, long long* t_dev,
+                                      const float* abar, float eta, float* out, float* out2, int advance,
+                                      sdmi_stream_t stream) {
   if (!xt || !eps || !out || !ts || !tp || !idx || !abar || n <= 0) return -1;
   sdmi_rt::launch(ddim_prev_dev_kernel, dim3(grid_for(n)), dim3(NT), 0, (hipStream_t)stream, xt, eps, noise, n, ts, tp,
-                  (const long long*)idx, abar, eta, out);
+                  (const long long*)idx, abar, eta, out, out2);
   SDMI_CHECK_LAUNCH();
   if (advance) {
     sdmi_rt::launch(ddim_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ts, idx, t_dev);
     SDMI_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+extern "C" int sdmi_ddim_prev_dev(const float* xt, const float* eps, const float* noise, long long n,
+                                  const long long* ts, const long long* tp, long long* idx, long long* t_dev,
+                                  const float* abar, float eta, float* out, int advance, sdmi_stream_t stream) {
+  return sdmi_ddim_prev_dev_dup(xt, eps, noise, n, ts, tp, idx, t_dev, abar, eta, out, nullptr, advance, stream);
+}
+
+extern "C" int sdmi_cfg_combine(const float* eps_cond, const float* eps_uncond, long long n, float scale, float* out,
+                                sdmi_stream_t stream) {
+  if (!eps_cond || !eps_uncond || !out || n <= 0) return -1;
+  sdmi_rt::launch(cfg_combine_kernel, dim3(grid_for(n)), dim3(NT), 0, (hipStream_t)stream, eps_cond, eps_uncond, n,
+                  scale, out);
+  SDMI_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sdmi_cfg_combine_nhwc(const void* pred, int src_f32, int ld, int B, int C, int HW, float scale,
+                                     float* dst, sdmi_stream_t stream) {
+  if (!pred || !dst || B <= 0 || C <= 0 || HW <= 0 || ld < C) return -1;
+  sdmi_rt::launch(cfg_combine_nhwc_kernel, dim3(grid_for((long long)B * C * HW)), dim3(NT), 0, (hipStream_t)stream,
+                  pred, src_f32, ld, B, C, HW, scale, dst);
+  SDMI_CHECK_LAUNCH();
   return 0;
 }
 

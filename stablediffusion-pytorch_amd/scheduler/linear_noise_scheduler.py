@@ -150,8 +150,17 @@ class DDIMSampler(nn.Module):
     @torch.no_grad()
     def sample_one_step(self, x_t, time_step, prev_time_step, eta, noise=None):
         _require_cuda(x_t, "DDIMSampler")
-        t = torch.full((x_t.shape[0],), int(time_step), device=x_t.device, dtype=torch.long)
-        eps = self.model(x_t, t, self.cond_input).float().contiguous()
+        B = x_t.shape[0]
+        cond2 = getattr(self, "_cond2", None)
+        if cond2 is not None:  # classifier-free guidance: one doubled-batch call [cond | uncond], then the combine
+            t = torch.full((2 * B,), int(time_step), device=x_t.device, dtype=torch.long)
+            eps = self.model(torch.cat([x_t, x_t]), t, cond2).float().contiguous()
+            _lib.check(_lib.lib().sdmi_cfg_combine(eps.data_ptr(), eps[B:].data_ptr(), eps.numel() // 2,
+                                                   self._scale, eps.data_ptr(), K._stream()), "sdmi_cfg_combine")
+            eps = eps[:B]
+        else:
+            t = torch.full((B,), int(time_step), device=x_t.device, dtype=torch.long)
+            eps = self.model(x_t, t, self.cond_input).float().contiguous()
         if noise is None:
             noise = torch.randn_like(x_t)  # drawn every step, as the reference does (:171)
         x = x_t.float().contiguous()
@@ -176,36 +185,61 @@ class DDIMSampler(nn.Module):
 
     @torch.no_grad()
     def forward(self, x_t, cond_input, uncond_input, steps=1, method="linear", eta=0.0, only_return_x_0=True,
-                interval=1, captured=True, seed=None):
+                interval=1, captured=True, seed=None, guidance_scale=1.0):
         """captured (default): a drop-in denoiser on the fused engine samples through sdmi.sampling.DDIMSampleLoop --
         the loop recorded once and replayed with device timestep tables and device noise (Philox) -- when only x_0 is
         returned; otherwise (intermediates, foreign models) every step is issued eagerly with torch.randn_like noise as
         the reference does (:200). seed=None (default): every call draws fresh noise, its Philox stream chosen by
         torch's default generator (as the reference's randn_like is, so torch.manual_seed makes a call repeatable);
-        an explicit seed makes every call with that seed repeat the same noise."""
+        an explicit seed makes every call with that seed repeat the same noise.
+        guidance_scale: classifier-free guidance as the reference's generator scripts apply it through their
+        _GuidedWrapper (batch_condition_image_generator_single.py:249-262; sdmi.sampling.guidance_mode): 1 samples with
+        cond_input alone (the default: uncond_input is not read), 0 with uncond_input alone, every other scale runs
+        ONE doubled-batch forward [cond | uncond] per step and combines uncond + scale * (cond - uncond) with
+        sdmi_cfg_combine -- inside the captured step and on the eager path alike."""
+        from sdmi.sampling import cat_conditions, check_uncond, guidance_mode
+        mode = guidance_mode(guidance_scale)
+        if mode != "cond":
+            if uncond_input is None:
+                raise ValueError(f"guidance_scale={guidance_scale} needs uncond_input")
+            check_uncond(cond_input, uncond_input)
+        if mode == "uncond":  # the unconditional forward alone: a plain run on uncond_input
+            cond_input = uncond_input
+        guided = mode == "guided"
         self.cond_input = cond_input
         self.uncond_input = uncond_input
         if captured and only_return_x_0 and hasattr(self.model, "_sdmi"):
             from sdmi.module_glue import engine_path_ok
             from sdmi.sampling import DDIMSampleLoop
             if engine_path_ok(self.model):
-                cond_key = tuple(sorted((k, v.data_ptr(), tuple(v.shape)) for k, v in (cond_input or {}).items()
+                def tensors(c):
+                    return tuple(sorted((k, v.data_ptr(), tuple(v.shape)) for k, v in (c or {}).items()
                                         if isinstance(v, torch.Tensor)))
+                cond_key = tensors(cond_input)
                 # the parameters' identity is part of the key: replaced (not updated-in-place) weights rebuild the loop
                 params = tuple(p.data_ptr() for p in self.model.parameters())
                 key = (tuple(x_t.shape), steps, method, float(eta), -1 if seed is None else int(seed), cond_key,
                        hash(params))
+                if guided:
+                    key += (tensors(uncond_input), float(guidance_scale))
                 loop = getattr(self, "_loop", None)
                 if loop is None or self._loop_key != key:
+                    kw = dict(uncond_input=uncond_input, guidance_scale=guidance_scale) if guided else {}
                     loop = DDIMSampleLoop(self.model, self.alpha_t_bar, tuple(x_t.shape), cond_input, steps=steps,
-                                          method=method, eta=eta, seed=0 if seed is None else seed)
+                                          method=method, eta=eta, seed=0 if seed is None else seed, **kw)
                     self._loop, self._loop_key = loop, key
                 draw = loop.fresh_draw() if seed is None else 0
                 return loop.run(x_t.float(), draw=draw).clone()
         ts, tp = self.time_steps(self.T, steps, method)
         x = [x_t]
-        for i in reversed(range(0, steps)):
-            x_t = self.sample_one_step(x_t, ts[i], tp[i], eta)
-            if not only_return_x_0 and ((steps - i) % interval == 0 or i == 0):
-                x.append(torch.clip(x_t, -1.0, 1.0))
+        # (the eager guided step reads the conditions concatenated once per call)
+        self._cond2 = cat_conditions(cond_input, uncond_input) if guided else None
+        self._scale = float(guidance_scale)
+        try:
+            for i in reversed(range(0, steps)):
+                x_t = self.sample_one_step(x_t, ts[i], tp[i], eta)
+                if not only_return_x_0 and ((steps - i) % interval == 0 or i == 0):
+                    x.append(torch.clip(x_t, -1.0, 1.0))
+        finally:
+            self._cond2 = None
         return x_t if only_return_x_0 else torch.stack(x, dim=1)

@@ -154,6 +154,10 @@ SIGNATURES = {
     "sdmi_ddim_prev": ([_P, _P, _P, _L, _F, _F, _F, _P, _P], _I),
     "sdmi_ddim_prev_dev": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _F, _P, _I, _P], _I),
     "sdmi_affine_step": ([_P, _P, _P, _L, _F, _F, _F, _P, _P], _I),
+    "sdmi_cfg_combine": ([_P, _P, _L, _F, _P, _P], _I),
+    "sdmi_cfg_combine_nhwc": ([_P, _I, _I, _I, _I, _I, _F, _P, _P], _I),
+    "sdmi_ddpm_prev_dup": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P], _I),
+    "sdmi_ddim_prev_dev_dup": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _F, _P, _P, _I, _P], _I),
     "sdmi_mse_patch": ([_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P], _I),
     "sdmi_randn": ([_P, _L, ctypes.c_ulonglong, _P, _I, _P], _I),
     "sdmi_step_draw": ([_P, _L, _P, _I, _I, _P, _P, _P, _L, ctypes.c_float, _P, ctypes.c_float, ctypes.c_ulonglong,

@@ -374,6 +374,15 @@ class DiTEngine:
                                                   self.L["p"], out.data_ptr(), K._stream()), "sdmi_tokens_to_nchw")
         return out
 
+    def guided_to_nchw(self, pred, B, H, W, scale):
+        """Classifier-free guidance on a doubled-batch prediction (token layout: samples [0, B) conditional, the rest
+        unconditional): tokens -> NCHW at 2B, then uncond + scale * (cond - uncond) in place of the conditional half."""
+        out = self.pred_to_nchw(pred, 2 * B, H, W)
+        n = out.numel() // 2
+        _lib.check(_lib.lib().sdmi_cfg_combine(out.data_ptr(), out[B:].data_ptr(), n, float(scale), out.data_ptr(),
+                                               K._stream()), "sdmi_cfg_combine")
+        return out[:B]
+
     def dpred_from_nchw(self, d):
         B, C, H, W = d.shape
         p = self.L["p"]

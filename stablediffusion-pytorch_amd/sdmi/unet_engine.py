@@ -1099,6 +1099,14 @@ class UNetEngine:
                                                 K._stream()), "sdmi_nhwc_to_nchw")
         return out
 
+    def guided_to_nchw(self, pred, B, H, W, scale):
+        """Classifier-free guidance on a doubled-batch prediction (rows [0, B*H*W) conditional, the rest
+        unconditional): uncond + scale * (cond - uncond) as (B, C, H, W), in the launch pred_to_nchw would be."""
+        out = torch.empty(B, self.im_channels, H, W, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().sdmi_cfg_combine_nhwc(pred.data_ptr(), 1, 8, B, self.im_channels, H * W, float(scale),
+                                                    out.data_ptr(), K._stream()), "sdmi_cfg_combine_nhwc")
+        return out
+
     def dpred_from_nchw(self, d):
         B, C, H, W = d.shape
         dpred = torch.empty(B * H * W, 8, dtype=torch.bfloat16, device=self.device)
