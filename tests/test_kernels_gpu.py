@@ -29,7 +29,15 @@ def relerr(a, b):
                                           # 32^2), 8-channel strips (C=256), 64-thread workgroups (4^2), ragged P
                                           (32, 32, 384, 32, True), (32, 32, 256, 32, False), (32, 4, 768, 32, True),
                                           (4, 30, 384, 32, True), (32, 16, 512, 32, True),
-                                          (1024, 2, 512, 32, True)])  # 256-channel strips on 64 threads
+                                          (1024, 2, 512, 32, True),  # 256-channel strips on 64 threads
+                                          # the single-pass shapes the cases above leave out: 256 threads x 1 row
+                                          # (40-channel strips), 512 x 4, 512 x 2 (160-channel strips), 1024 x 2
+                                          # (72-channel strips)
+                                          (128, 7, 128, 32, True), (1, 19, 96, 32, True), (128, 7, 512, 32, False),
+                                          (256, 15, 96, 32, True),
+                                          # too many pixels for one pass: gn_stats / gn_bwd_reduce (72-channel strips,
+                                          # 16 pixel splits, batch tail) + the elementwise kernels
+                                          (2, 56, 96, 32, True)])
 def test_groupnorm_fwd_bwd(B, H, C, G, silu):
     k = K()
     torch.manual_seed(0)
@@ -155,7 +163,8 @@ def test_groupnorm_bwd_from_gemm_statistics(B, H, C, prod, silu, splits, monkeyp
 
 
 @pytest.mark.parametrize("shapes", [[(2, 8, 64)], [(32, 32, 384), (32, 16, 512), (32, 4, 768)],
-                                    [(4, 8, 96)] * 17])  # 17 jobs: two grouped launches
+                                    [(4, 8, 96)] * 17,  # 17 jobs: two grouped launches
+                                    [(2, 56, 96)]])  # the multi-pass backward (reduce + apply kernels)
 def test_groupnorm_bwd_deferred_sums_match_inline(shapes):
     """sdmi_gn_bwd_rows (dgamma / dbeta as per-sample rows, no batch tail) + sdmi_gn_rows_sum_grouped over several
     GroupNorms against the inline sdmi_gn_bwd: dx bitwise equal, dgamma / dbeta to fp32 summation order (the inline
