@@ -149,6 +149,8 @@ int sdmi_gemm_grouped(const sdmi_gemm_desc* d, int ngroups, void* workspace, siz
  * Replaces the core of torch nn.MultiheadAttention as called at models/blocks.py:128 (self) and
  * :140 (cross, kv = context_proj(context)): softmax((q / sqrt(d)) k^T) v per head, head h in columns
  * [h*d, h*d+d) of row-major [batch*len][ld] buffers; d % 8 == 0, d <= 64; S (keys) may differ from N.
+ * Every bf16 operand and output (q, k, v, o, dout, out, dq, dk, dv) has a 16-byte aligned base and a row stride
+ * ld % 8 == 0 (rows are read in 16-byte chunks): otherwise -2, as for an unsupported d; -1 for a non-positive size.
  * lse: fp32 [B*H][N], base 2: log2 sum_j 2^(s_ij log2 e) (saved for the backward).  Backward: dq, dk, dv (no atomics); delta_ws fp32 [B*H*N].
  * ------------------------------------------------------------------------------------------- */
 int sdmi_attn_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,

@@ -847,6 +847,14 @@ __device__ unsigned g_attn_counters[ATTN_CTR_SLOTS * ATTN_CTR_SLOT];
 int check_args(const AttnArgs& a) {
   if (a.B <= 0 || a.H <= 0 || a.N <= 0 || a.S <= 0 || a.d <= 0) return -1;
   if (a.d % 8 || a.d > 64) return -2;
+  // rows are read as 16-B chunks and stored as 8-B ones at head offsets h*d (d % 8 == 0): every base 16-B aligned,
+  // every row stride a multiple of 8 elements (operands an entry point does not take are null / 0 here)
+  const void* ptrs[] = {a.q, a.k, a.v, a.o, a.dout, a.out, a.dq, a.dk, a.dv};
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 15) return -2;
+  const int lds[] = {a.ldq, a.ldk, a.ldv, a.ldo, a.lddo, a.lddq, a.lddk, a.lddv};
+  for (int ld : lds)
+    if (ld % 8) return -2;
   return 0;
 }
 
