@@ -307,7 +307,8 @@ int sdmi_mse_patch(const float* pred, int ld, const float* target, int B, int C,
  *  sdmi_pointwise_in: post_quant_conv (1x1, fp32) of an NCHW fp32 latent into NHWC bf16 [P][ld] (tail zeroed).
  * ------------------------------------------------------------------------------------------- */
 /*  sdmi_vq_bwd      : training backward of the latent interface (train_vqvae_celebhq.py:405-430, recon + codebook
- *                     + commitment terms; LPIPS / GAN out of scope): from dzin (gradient of post_quant_conv's output,
+ *                     + commitment terms; LPIPS enters through the reconstruction gradient, see the LPIPS section; the
+ *                     GAN term is out of scope): from dzin (gradient of post_quant_conv's output,
  *                     NHWC bf16) -> post_quant_conv dW/db, the straight-through gradient of the pre-quantisation
  *                     latent plus commitment_beta * 2 (x - q) / n, pre_quant_conv dW/db and dz_enc (NHWC bf16
  *                     gradient of encoder_conv_out's output), and the codebook gradient codebook_weight * 2 (q - x) / n
@@ -326,6 +327,44 @@ int sdmi_vq_quantize(const float* z, int ldz, const float* w, const float* b, co
                      int HW, int C, float* zq, long long* idx, float* xq, float* ws, float* loss, sdmi_stream_t stream);
 int sdmi_pointwise_in(const float* z, int B, int C, int HW, const float* w, const float* b, int cout, void* out,
                       int ld, sdmi_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * LPIPS perceptual loss (models/lpips.py) around the VGG16 convolutions (sdmi_gemm, act 2 / 3). NHWC bf16
+ * activations, fp32 arithmetic, fixed-order reductions (bitwise repeatable, no atomics).
+ *  sdmi_lpips_prep       : ScalingLayer + packing. out [2B*H*W][8] bf16 = (x - shift[c]) / scale[c] of in0 (rows
+ *                          [0, B*H*W)) and in1 (the rest), x -> 2x - 1 first under normalize, channels 3..7 zero. A
+ *                          source is NCHW fp32 (B,3,H,W) (inX_nhwc = 0) or NHWC fp32 [B*H*W][8] (inX_nhwc = 1).
+ *  sdmi_lpips_image_grad : d [B*H*W][8] bf16 (gradient of the scaled image) -> d_c / scale[c] (x 2 under normalize),
+ *                          written to out_nchw (B,3,H,W) fp32 and / or added into channels 0..2 of acc_nhwc
+ *                          [B*H*W][8] bf16 (fp32 sum, one rounding; channels 3..7 untouched). With mse_pred (NHWC fp32
+ *                          [B*H*W][8]) and mse_target (NCHW fp32), both or neither: acc_nhwc is written whole instead,
+ *                          sdmi_mse's gradient 2 (pred - target) / (3 B H W) plus the image gradient, summed in fp32
+ *                          and rounded once, channels 3..7 zero.
+ *  sdmi_maxpool2_fwd/bwd : nn.MaxPool2d(2, 2) on (N,H,W,C) bf16, C % 8 == 0, floor mode. The backward recomputes the
+ *                          argmax from x (first maximum in window scan order, as torch) and fully overwrites dx (the
+ *                          dropped odd row / column gets zero).
+ *  sdmi_lpips_dist_fwd   : one tap f [2B*P][ld] (C in {64,128,256,512}): u = f / max(|f|, 1e-12) per pixel,
+ *                          val[b] (+)= (1/P) sum_p sum_c w[c] (u0 - u1)^2 (accumulate = 0 overwrites). rn (nullable):
+ *                          the 2B*P inverse norms the backward needs. ws: sdmi_lpips_dist_workspace(B, P, C) bytes.
+ *  sdmi_lpips_dist_bwd   : gradient of the rows of image `side` (0 / 1), B*P rows into dy: df = coef rn_a (t - u_a
+ *                          sum_k t_k u_a,k), t_c = 2 w_c (u_a,c - u_o,c), coef = (g ? g[b] : 1) * gscale / P;
+ *                          dy = f > 0 ? df + addend : 0 (addend nullable: the gradient from the next slice). Rows
+ *                          that are all zero give exact zeros.
+ *  sdmi_lpips_mean       : out[0] = scale * sum_b val[b].
+ * ------------------------------------------------------------------------------------------- */
+int sdmi_lpips_prep(const float* in0, int in0_nhwc, const float* in1, int in1_nhwc, int B, int H, int W,
+                    const float* shift, const float* scale, int normalize, void* out, sdmi_stream_t stream);
+int sdmi_lpips_image_grad(const void* d, int B, int H, int W, const float* scale, int normalize, float* out_nchw,
+                          void* acc_nhwc, const float* mse_pred, const float* mse_target, sdmi_stream_t stream);
+int sdmi_maxpool2_fwd(const void* x, int N, int H, int W, int C, void* y, sdmi_stream_t stream);
+int sdmi_maxpool2_bwd(const void* x, const void* dy, int N, int H, int W, int C, void* dx, sdmi_stream_t stream);
+size_t sdmi_lpips_dist_workspace(int B, int P, int C);
+int sdmi_lpips_dist_fwd(const void* f, int ld, const float* w, int B, int P, int C, float* rn, float* ws, int accumulate,
+                        float* val, sdmi_stream_t stream);
+int sdmi_lpips_dist_bwd(const void* f, int ld, const float* w, const float* rn, const float* g, float gscale, int B,
+                        int P, int C, int side, const void* addend, int ld_add, void* dy, int ld_dy,
+                        sdmi_stream_t stream);
+int sdmi_lpips_mean(const float* val, int B, float scale, float* out, sdmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Sampling steps (scheduler/linear_noise_scheduler.py), fp32 elementwise, bit-exact to the reference given the

@@ -11,8 +11,8 @@
 //                (codebook == commitment) loss mean((q - x)^2).
 //  pointwise_in: post_quant_conv (1x1, fp32) of an NCHW fp32 latent straight into the NHWC bf16 operand of
 //                decoder_conv_in (vqvae.py:141-144), zero-padding the channel tail.
-//  vq_bwd      : the training backward of the latent interface (train_vqvae_celebhq.py:405-430 without the
-//                LPIPS / GAN terms): post_quant_conv backward, the straight-through estimator (dL/dx += dL/dz_q),
+//  vq_bwd      : the training backward of the latent interface (train_vqvae_celebhq.py:405-430 without the GAN
+//                term; LPIPS reaches it inside the reconstruction gradient, lpips.hip): post_quant_conv backward, the straight-through estimator (dL/dx += dL/dz_q),
 //                the commitment term beta * mean((sg[q] - x)^2), pre_quant_conv backward into the bf16 NHWC
 //                gradient of encoder_conv_out; the 1x1-conv weight / bias gradients as per-block partials summed in
 //                a fixed order (deterministic). vq_codebook_grad: the codebook term w * mean((q - sg[x])^2) into the

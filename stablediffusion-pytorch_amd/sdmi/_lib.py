@@ -166,6 +166,14 @@ SIGNATURES = {
     "sdmi_vq_bwd_workspace": ([], _SZ),
     "sdmi_vq_bwd": ([_P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _F, _F, _P, _I, _P, _P, _P, _P, _P, _P,
                      _P, _P, _P], _I),
+    "sdmi_lpips_prep": ([_P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P], _I),
+    "sdmi_lpips_image_grad": ([_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P], _I),
+    "sdmi_maxpool2_fwd": ([_P, _I, _I, _I, _I, _P, _P], _I),
+    "sdmi_maxpool2_bwd": ([_P, _P, _I, _I, _I, _I, _P, _P], _I),
+    "sdmi_lpips_dist_workspace": ([_I, _I, _I], _SZ),
+    "sdmi_lpips_dist_fwd": ([_P, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P], _I),
+    "sdmi_lpips_dist_bwd": ([_P, _I, _P, _P, _P, _F, _I, _I, _I, _I, _P, _I, _P, _I, _P], _I),
+    "sdmi_lpips_mean": ([_P, _I, _F, _P, _P], _I),
     "sdmi_plan_begin": ([], _I),
     "sdmi_plan_end": ([ctypes.POINTER(ctypes.c_void_p)], _I),
     "sdmi_plan_recording": ([], _I),

@@ -206,9 +206,10 @@ def conv_geom(ih, iw, cin, ldx, kh, kw, oh, ow, sy, sx, oy0, ox0):
 
 
 def conv_fwd(x, B, H, W, cin, ldx, wpk, cout, kh, kw, stride, pad, out, ldo, *, bias=None, rowbias=None,
-             rb_ld=0, resid=None, ldr=0, act=0, n_store=0, x2=None, cin2=0, bias2=None, ldw=0, gn=None):
+             rb_ld=0, resid=None, ldr=0, act=0, n_store=0, x2=None, cin2=0, bias2=None, ldw=0, gn=None, aux=None):
     """y[b,oy,ox,co] = sum_{ty,tx,ci} x[b, oy*s+ty-pad, ox*s+tx-pad, ci] * wpk[co, (ty*kw+tx)*cin + ci].
-    x: NHWC bf16 buffer (row stride ldx), wpk: bf16 [cout][kh*kw*cin]."""
+    x: NHWC bf16 buffer (row stride ldx), wpk: bf16 [cout][kh*kw*cin]. act 3 with aux (the saved ReLU output, same
+    grid as y): the data gradient of a convolution whose input was a ReLU output."""
     OH = (H + 2 * pad - kh) // stride + 1
     OW = (W + 2 * pad - kw) // stride + 1
     g = conv_geom(H, W, cin, ldx, kh, kw, OH, OW, stride, stride, -pad, -pad)
@@ -218,7 +219,7 @@ def conv_fwd(x, B, H, W, cin, ldx, wpk, cout, kh, kw, stride, pad, out, ldo, *, 
     return gemm(B * OH * OW, cout, K1 + cin2, x, _lib.A_CONV, 0, wpk, _lib.B_NK, ldw or (K1 + cin2), out, ldo,
                 geom=g, bias=bias, rowbias=rowbias, rb_ld=(rb_ld or cout) if rowbias is not None else 0,
                 rb_div=OH * OW, resid=resid, ldr=ldr, act=act, n_store=n_store,
-                a2=x2, lda2=ld_of(x2) if x2 is not None else 0, k_split=K1, bias2=bias2, gn=gn)
+                a2=x2, lda2=ld_of(x2) if x2 is not None else 0, k_split=K1, bias2=bias2, gn=gn, aux=aux)
 
 
 def conv_wgrad(dy, ldy, x, B, H, W, cin, ldx, cout, kh, kw, stride, pad, out, OH, OW, *, perm=True, cvalid=0,
@@ -573,3 +574,65 @@ def cond_wgrad(dxin, ld, cx, B, H, W, mask, cmi, cmo, dw, keep):
     else:
         _lib.check(L.sdmi_cond_wgrad(_ptr(dxin), ld, cx, B, H, W, _ptr(mask), cmi, mask.shape[2], mask.shape[3], cmo,
                                      _ptr(dw), _p(keep), _stream()), "sdmi_cond_wgrad")
+
+
+# ------------------------------------------------------------------------------------------------
+# LPIPS (csrc/lpips.hip): image scaling in / out, 2x2 max-pool pair, per-tap distance and its backward
+# ------------------------------------------------------------------------------------------------
+def lpips_prep(in0, nhwc0, in1, nhwc1, B, H, W, shift, scale, normalize, out):
+    """out [2B*H*W][8] bf16 = ScalingLayer of in0 (first half of the rows) and in1; inX NCHW fp32 (B,3,H,W) or, with
+    nhwcX, NHWC fp32 [B*H*W][8]."""
+    with _Prof("lpips_prep", 0, f"B={B} H={H} W={W}"):
+        check(_lib.lib().sdmi_lpips_prep(_p(in0), 1 if nhwc0 else 0, _p(in1), 1 if nhwc1 else 0, B, H, W, _p(shift),
+                                         _p(scale), 1 if normalize else 0, _p(out), _stream()), "sdmi_lpips_prep")
+    return out
+
+
+def lpips_image_grad(d, B, H, W, scale, normalize, out_nchw=None, acc_nhwc=None, mse=None):
+    """Image gradient from the scaled-image gradient d [B*H*W][8] bf16: into out_nchw (B,3,H,W) fp32 and / or added
+    into channels 0..2 of acc_nhwc [B*H*W][8] bf16. mse = (pred NHWC fp32 [B*H*W][8], target NCHW fp32): acc_nhwc is
+    written whole instead, the gradient of mse() plus the image gradient, summed in fp32 and rounded once."""
+    pred, target = mse if mse is not None else (None, None)
+    with _Prof("lpips_image_grad", 0, f"B={B} H={H} W={W}"):
+        check(_lib.lib().sdmi_lpips_image_grad(_p(d), B, H, W, _p(scale), 1 if normalize else 0, _p(out_nchw),
+                                               _p(acc_nhwc), _p(pred), _p(target), _stream()), "sdmi_lpips_image_grad")
+
+
+def maxpool2_fwd(x, N, H, W, C, y):
+    """nn.MaxPool2d(2, 2) (floor) on compact NHWC bf16: x [N*H*W][C] -> y [N*(H//2)*(W//2)][C]."""
+    assert ld_of(x) == C and ld_of(y) == C
+    with _Prof("maxpool2_fwd", 0, f"N={N} H={H} W={W} C={C}"):
+        check(_lib.lib().sdmi_maxpool2_fwd(_p(x), N, H, W, C, _p(y), _stream()), "sdmi_maxpool2_fwd")
+    return y
+
+
+def maxpool2_bwd(x, dy, N, H, W, C, dx):
+    """dx [N*H*W][C] (fully overwritten) from dy [N*(H//2)*(W//2)][C] and the saved input x."""
+    assert ld_of(x) == C and ld_of(dy) == C and ld_of(dx) == C
+    with _Prof("maxpool2_bwd", 0, f"N={N} H={H} W={W} C={C}"):
+        check(_lib.lib().sdmi_maxpool2_bwd(_p(x), _p(dy), N, H, W, C, _p(dx), _stream()), "sdmi_maxpool2_bwd")
+    return dx
+
+
+def lpips_dist_fwd(f, w, B, P, C, val, accumulate, rn=None):
+    """val[b] (+)= mean_p sum_c w[c] (u0 - u1)^2 over the tap f [2B*P][C]; rn (fp32 [2B*P], optional): the inverse
+    norms for lpips_dist_bwd."""
+    L = _lib.lib()
+    ws = torch.empty(max(L.sdmi_lpips_dist_workspace(B, P, C) // 4, 1), dtype=torch.float32, device=f.device)
+    with _Prof("lpips_dist_fwd", 0, f"B={B} P={P} C={C}"):
+        check(L.sdmi_lpips_dist_fwd(_p(f), ld_of(f), _p(w), B, P, C, _p(rn), _p(ws), 1 if accumulate else 0, _p(val),
+                                    _stream()), "sdmi_lpips_dist_fwd")
+
+
+def lpips_dist_bwd(f, w, rn, B, P, C, side, dy, *, g=None, gscale=1.0, addend=None):
+    """dy [B*P][C] = gradient of the tap rows of image `side` for dL/dval[b] = g[b] * gscale (g: device fp32 (B,) or
+    None for 1), plus addend, through the tap's ReLU."""
+    with _Prof("lpips_dist_bwd", 0, f"B={B} P={P} C={C}"):
+        check(_lib.lib().sdmi_lpips_dist_bwd(_p(f), ld_of(f), _p(w), _p(rn), _p(g), float(gscale), B, P, C, side,
+                                             _p(addend), ld_of(addend) if addend is not None else 0, _p(dy),
+                                             ld_of(dy), _stream()), "sdmi_lpips_dist_bwd")
+    return dy
+
+
+def lpips_mean(val, B, scale, out):
+    check(_lib.lib().sdmi_lpips_mean(_p(val), B, float(scale), _p(out), _stream()), "sdmi_lpips_mean")

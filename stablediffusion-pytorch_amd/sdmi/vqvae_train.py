@@ -10,8 +10,10 @@ The blocks are the UNet engine's (sdmi.unet_engine: same resnet / self-attention
 kernels and backward schedule, t_emb_dim=None so no time-embedding terms); the latent interface is two kernels:
 sdmi_vq_quantize (pre_quant_conv + cdist/argmin + STE output, vqvae.py:93-126) and sdmi_vq_bwd (post_quant_conv
 backward, straight-through gradient + commitment term, pre_quant_conv backward, the codebook rows' gradient).
-LPIPS and the PatchGAN terms of the reference trainer are out of scope (LPIPS needs a pretrained VGG16
-download); so is its fp32-only arithmetic: activations are bf16 here, accumulation fp32, master weights fp32."""
+The reference's LPIPS term is optional (VQVAETrainer(perceptual_weight=, lpips_state=): sdmi.lpips_engine on the
+reconstruction, its image gradient added into the reconstruction gradient before the backward; the pretrained weights
+are supplied by the caller). The PatchGAN term of the reference trainer is out of scope; so is its fp32-only
+arithmetic: activations are bf16 here, accumulation fp32, master weights fp32."""
 import torch
 import torch.distributed as dist
 
@@ -328,13 +330,16 @@ class VQVAETrainEngine(UNetEngine):
 
 
 class VQVAETrainer:
-    """The generator step of train_vqvae_celebhq.py:405-470 without LPIPS / GAN: forward, recon MSE + codebook
+    """The generator step of train_vqvae_celebhq.py:405-470 without the GAN term: forward, recon MSE + codebook
     (weight codebook_weight) + commitment (commitment_beta) losses, backward, Adam(lr, betas=(0.5, 0.999)).
+    With lpips_state (an LPIPS state dict) and a non-zero perceptual_weight the step adds perceptual_weight *
+    mean_b LPIPS(out, im) (train_vqvae_celebhq.py:427-428); by default no LPIPS engine exists and the step is unchanged.
     Flat fp32 parameter / gradient / moment buffers; the step never synchronises with the host. With N > 1 ranks
     the gradients are averaged over the process group (one bucketed all-reduce after the backward) before Adam."""
 
     def __init__(self, cfg, state_dict, device, *, im_channels=3, lr=2e-5, betas=(0.5, 0.999), eps=1e-8,
-                 codebook_weight=1.0, commitment_beta=0.2, group=None, bucket_bytes=64 << 20):
+                 codebook_weight=1.0, commitment_beta=0.2, group=None, bucket_bytes=64 << 20,
+                 perceptual_weight=0.0, lpips_state=None):
         from .reducer import BucketReducer
         self.cfg = cfg
         self.device = torch.device(device)
@@ -359,6 +364,16 @@ class VQVAETrainer:
         self.engine.refresh_weights()
         self.vq_loss = None
         self.indices = None
+        self.lpips = None
+        if perceptual_weight and lpips_state is None:
+            raise ValueError("perceptual_weight is set but no LPIPS weights were given (lpips_state=)")
+        if perceptual_weight and lpips_state is not None:
+            if im_channels != 3:
+                raise ValueError("the LPIPS term needs 3-channel images")
+            from .lpips_engine import LPIPSEngine
+            self.hp["pw"] = float(perceptual_weight)
+            self.lpips = LPIPSEngine(lpips_state, self.device)
+            self.lp_loss = torch.zeros(1, dtype=torch.float32, device=self.device)  # the weighted perceptual loss
 
     def step(self, im):
         """One generator step on a device image batch (B, im_channels, H, W) fp32 in [-1, 1]."""
@@ -367,7 +382,15 @@ class VQVAETrainer:
         self._shape = (B, C, H, W)
         out, ctx = eng.forward(im)
         dout = eng.new_dpred(B, H, W)
-        K.mse(out, 8, plan.as_operand(im), B, C, H * W, 1.0, dout, self.state[S_LOSS:S_LOSS + 1])
+        if self.lpips is None:
+            K.mse(out, 8, plan.as_operand(im), B, C, H * W, 1.0, dout, self.state[S_LOSS:S_LOSS + 1])
+        else:  # + pw * mean_b LPIPS(out, im): gradient pw / B per sample, to the reconstruction only
+            imo = plan.as_operand(im)
+            K.mse(out, 8, imo, B, C, H * W, 1.0, None, self.state[S_LOSS:S_LOSS + 1])  # the loss alone
+            val, lctx = self.lpips.forward(out, imo, nhwc=(True, False), shape=(B, H, W))
+            K.lpips_mean(val, B, hp["pw"] / B, self.lp_loss)
+            # dout = MSE gradient + LPIPS image gradient, summed in fp32 and rounded to bf16 once
+            self.lpips.backward(lctx, None, want=(True, False), gscale=hp["pw"] / B, acc=dout, mse=(out, imo))
         if self.reducer is not None:
             self.reducer.reset()
         eng.backward(ctx, dout, hp["cw"], hp["beta"])
@@ -390,11 +413,16 @@ class VQVAETrainer:
         return self.state
 
     def losses(self):
-        """Host dict of the last step's losses (synchronises): recon, codebook (weighted), commitment (weighted)."""
+        """Host dict of the last step's losses (synchronises): recon, codebook (weighted), commitment (weighted) and,
+        with the LPIPS term, perceptual (weighted)."""
         rec = self.state[S_LOSS].item()
         vq = self.vq_loss.item()
-        return dict(recon=rec, codebook=self.hp["cw"] * vq, commitment=self.hp["beta"] * vq,
-                    total=rec + (self.hp["cw"] + self.hp["beta"]) * vq)
+        d = dict(recon=rec, codebook=self.hp["cw"] * vq, commitment=self.hp["beta"] * vq,
+                 total=rec + (self.hp["cw"] + self.hp["beta"]) * vq)
+        if self.lpips is not None:
+            d["perceptual"] = self.lp_loss.item()
+            d["total"] += d["perceptual"]
+        return d
 
     def reconstruction(self):
         """The last step's decoder output as (B, im_channels, H, W) fp32."""
