@@ -543,6 +543,30 @@ int sdmi_plan_destroy(void* plan);
 int sdmi_plan_op_info(const void* plan, int i, int* kind, const char** name, int* grid, int* block, int* shmem);
 int sdmi_plan_op_stream(const void* plan, int i, sdmi_stream_t* stream); /* the stream op i was recorded on */
 int sdmi_plan_time_op(void* plan, int i, int warm, int iters, float* us);
+/* Cross-stream edges on the replay path. sdmi_plan_end compiles the recorded op list once into the list the replay
+ * issues (csrc/plan_edges.h): duplicate records aliased, records folded into the launch before them, dominated and
+ * clustered waits dropped -- the happens-before relation between launches, all-reduces and callouts unchanged. The
+ * recorded list stays as it is for the inspection calls above; `start` / `next` of sdmi_plan_replay index the list
+ * being replayed (pass 0, then what `next` returned).
+ * sdmi_plan_note_edge: `dst` waits for everything issued so far on `src`, through an event that never leaves the
+ *   plan (the caller issues the edge itself for the recording run): the plan creates and owns the event. Events given
+ *   to sdmi_plan_note_event / sdmi_plan_note_wait stay the caller's and are recorded on every replay.
+ * sdmi_plan_edge_info: recorded ops, compiled ops, records folded, records aliased, waits dropped, plan-owned events.
+ * sdmi_plan_op_edge: for recorded op i (an event record or a wait; -2 otherwise) the event's dense id in the plan,
+ *   whether the plan owns it, and the op's fate in the compiled list (0 kept, 1 folded, 2 aliased, 3 dropped).
+ * sdmi_plan_set_edges: process-wide diagnostic switch, read when a replay starts: 0 replays the recorded list
+ *   verbatim, 1 (default) the compiled list, 2 the compiled list without folding records into launches.
+ * sdmi_plan_edge_probe: device-side span (us) of a chain of `chain` short dependent kernels over `bytes` on one
+ *   stream with, per boundary: variant 0 nothing; 1 an event record and a second stream waiting on it; 2 the same with
+ *   the record folded into the launch; 3 `k` back-to-back waits on long-completed events of the second stream; 4 the
+ *   record alone, nothing waiting; 5 as 1 with no kernel on the second stream behind its wait.
+ *   nofence: the events carry hipEventDisableSystemFence. Averaged over `reps` chains after one untimed. */
+int sdmi_plan_note_edge(sdmi_stream_t src, sdmi_stream_t dst);
+int sdmi_plan_edge_info(const void* plan, int* recorded, int* compiled, int* folded, int* aliased, int* waits_dropped,
+                        int* owned_events);
+int sdmi_plan_op_edge(const void* plan, int i, int* event, int* owned, int* fate);
+int sdmi_plan_set_edges(int mode);
+int sdmi_plan_edge_probe(int variant, int nofence, int k, int chain, size_t bytes, int reps, float* span_us);
 
 /* ---------------------------------------------------------------------------------------------
  * Gradient all-reduce through RCCL, issued by the library on the caller's stream (replaces the DDP bucket hook's

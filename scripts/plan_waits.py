@@ -1,4 +1,6 @@
-"""Every cross-stream wait the recorded cond-UNet (or DiT) step puts on its MAIN stream, in issue order: the main-stream
+"""Every cross-stream edge the recorded cond-UNet (or DiT) step puts on its MAIN stream, in issue order, with what the
+compiled replay list makes of it (folded / aliased / dropped). Records: the main-stream kernel before the record and
+the streams that wait on the event. Waits: the main-stream
 kernel before and after the wait, and the stream and last kernel the awaited event follows. Read beside
 scripts/critical_path.py's main-stream idle gaps ("after X before Y"): a gap behind a wait whose producer finished long
 before is the wait's own cost, a gap with side-stream work inside it is a real dependency.
@@ -26,42 +28,28 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="cond-unet")
     a = ap.parse_args()
-    from sdmi import _lib, plan as P, streams
+    from sdmi import _lib, streams
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     streams.reserve(dev, n=streams.workload_streams(a.workload))
-    log = []  # (kind, stream, event) of every event record / wait, in plan order
-    rec, wait = P.record_event, P.wait_event
-
-    def rec_hook(ev, stream):
-        r = rec(ev, stream)  # (a torch event gets its HIP handle at its first record)
-        if P.RECORDING is not None:
-            log.append(("rec", stream.cuda_stream, ev.cuda_event))
-        return r
-
-    def wait_hook(stream, ev):
-        if P.RECORDING is not None:
-            log.append(("wait", stream.cuda_stream, ev.cuda_event))
-        return wait(stream, ev)
-
-    P.record_event, P.wait_event = rec_hook, wait_hook
-    cap = make(a.workload, dev)  # records the plan (the hooks see the recording's edges)
-    P.record_event, P.wait_event = rec, wait
+    cap = make(a.workload, dev)  # records the plan
     plan = cap.plan
     L = _lib.lib()
     n = plan.info()[0]
     kind, name, st = ctypes.c_int(), ctypes.c_char_p(), ctypes.c_void_p()
+    ev, owned, fate = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     ops = []
+    log = []  # (event id, plan-owned, fate in the compiled list) of every event record / wait, in plan order
     for i in range(n):
         _lib.check(L.sdmi_plan_op_info(plan.handle, i, ctypes.byref(kind), ctypes.byref(name), None, None, None), "info")
         _lib.check(L.sdmi_plan_op_stream(plan.handle, i, ctypes.byref(st)), "stream")
         ops.append((kind.value, st.value or 0, name.value.decode(errors="replace") if name.value else ""))
+        if kind.value in (1, 2):
+            _lib.check(L.sdmi_plan_op_edge(plan.handle, i, ctypes.byref(ev), ctypes.byref(owned), ctypes.byref(fate)), "edge")
+            log.append((ev.value, owned.value, fate.value))
     names = subprocess.run(["c++filt"], input="\n".join(o[2] or "-" for o in ops), capture_output=True,
                            text=True).stdout.splitlines()
     ops = [(k, s, short(nm) if k == 0 else "") for (k, s, _), nm in zip(ops, names)]
-    # the recording's own log is in step with the plan's event / wait ops (the first steps' log entries precede it)
-    edges = [o for o in ops if o[0] in (1, 2)]
-    log = log[len(log) - len(edges):]
     streams_seen = collections.Counter(s for k, s, _ in ops if k == 0)
     main = streams_seen.most_common(1)[0][0]
     sid = {s: i for i, (s, _) in enumerate(streams_seen.most_common())}
@@ -74,7 +62,7 @@ def main():
         if k == 0:
             lk[s] = nm
         elif k in (1, 2):
-            _, _, ev = log[lj]
+            ev = log[lj][0]
             lj += 1
             if k == 1:
                 later_src[ev] = (sid.get(s, -1), "previous step: " + lk.get(s, "(none)"))
@@ -82,6 +70,32 @@ def main():
     prev_main = "-"
     pending = []
     print(f"{n} ops; streams by launches: " + ", ".join(f"s{sid[s]}={c}" for s, c in streams_seen.most_common()))
+    info = plan.edge_info()
+    print(f"compiled list: {info['compiled']} ops of {info['recorded']} recorded ({info['folded']} records folded into "
+          f"their launch, {info['aliased']} aliased, {info['waits_dropped']} waits dropped; {info['owned_events']} "
+          f"plan-owned events)")
+    FATE = ("", " [folded]", " [aliased]", " [dropped]")
+    # every event record on the main stream: the kernel before it and the streams that wait on the event
+    waiters = collections.defaultdict(list)
+    lj = 0
+    for k, s, nm in ops:
+        if k in (1, 2):
+            if k == 2:
+                waiters[log[lj][0]].append(sid.get(s, -1))
+            lj += 1
+    print("main-stream records: <main kernel before> | event (plan-owned / caller's) [fate] | waited on by")
+    lj, before, nrec = 0, "-", collections.Counter()
+    for k, s, nm in ops:
+        if k == 0 and s == main:
+            before = nm
+        elif k in (1, 2):
+            e, own, ft = log[lj]
+            lj += 1
+            if k == 1 and s == main:
+                w = ", ".join(f"s{x}" for x in waiters[e]) or "nobody in the plan"
+                print(f"  {before:58s} | e{e} ({'plan-owned' if own else 'caller'}){FATE[ft]} | {w}")
+                nrec[FATE[ft].strip() or "kept"] += 1
+    print(f"{sum(nrec.values())} records on the main stream: " + ", ".join(f"{v} {k}" for k, v in sorted(nrec.items())))
     print("main-stream waits: <main kernel before> | waits on s<k> after <producer kernel> | <main kernel after>")
     count = collections.Counter()
     for k, s, nm in ops:
@@ -89,21 +103,21 @@ def main():
             last_kernel[s] = nm
             if s == main:
                 for w in pending:
-                    print(f"  {prev_main:58s} | s{w[0]} after {w[1]:50s} | {nm}")
+                    print(f"  {prev_main:58s} | s{w[0]} after {w[1]:50s} | {nm}{w[2]}")
                     count[(w[0], w[1][:30])] += 1
                 pending = []
                 prev_main = nm
             continue
         if k not in (1, 2):
             continue
-        kind_s, stream_s, ev = log[li]
+        ev, _, ft = log[li]
         li += 1
         if k == 1:
             event_src[ev] = (sid.get(s, -1), last_kernel.get(s, "(none)"))
         elif s == main:
             src = event_src.get(ev) or later_src.get(ev, (-1, "(recorded before the plan)"))
             if src[0] != sid[main]:
-                pending.append(src)
+                pending.append((src[0], src[1], FATE[ft]))
     print(f"{sum(count.values())} cross-stream waits on the main stream")
 
 

@@ -187,6 +187,11 @@ SIGNATURES = {
     "sdmi_plan_op_info": ([_P, _I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_char_p),
                            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], _I),
     "sdmi_plan_time_op": ([_P, _I, _I, _I, ctypes.POINTER(ctypes.c_float)], _I),
+    "sdmi_plan_note_edge": ([_P, _P], _I),
+    "sdmi_plan_edge_info": ([_P] + [ctypes.POINTER(ctypes.c_int)] * 6, _I),
+    "sdmi_plan_op_edge": ([_P, _I] + [ctypes.POINTER(ctypes.c_int)] * 3, _I),
+    "sdmi_plan_set_edges": ([_I], _I),
+    "sdmi_plan_edge_probe": ([_I, _I, _I, _I, _SZ, _I, ctypes.POINTER(ctypes.c_float)], _I),
     "sdmi_comm_load": ([ctypes.c_char_p], _I),
     "sdmi_comm_unique_id": ([_P], _I),
     "sdmi_comm_init": ([_P, _I, _I, ctypes.POINTER(ctypes.c_void_p)], _I),

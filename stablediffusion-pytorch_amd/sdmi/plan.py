@@ -11,7 +11,11 @@ C++ (one hipLaunchKernel each: same pointers, grids, streams and order), returni
 Per-step inputs live in static buffers refilled before each replay.
 
 Hazard model = the eager step's: replay issues the same operations on the same streams in the same order, and no
-memory of the pool is handed to anything outside the plan between replays."""
+memory of the pool is handed to anything outside the plan between replays. The stream / event edges are compiled once
+when the recording ends (csrc/plan_edges.h): duplicate records, dominated waits and records that can ride on the launch
+before them are not issued one by one, with the happens-before relation between the launches unchanged. StepPlan
+synchronises the device after recording, so the plan's own events, first recorded by the first replay, never stand
+for work of the recording run."""
 import ctypes
 
 import torch
@@ -73,13 +77,11 @@ def wait_event(stream, ev):
 
 
 def wait_stream(dst, src):
-    """dst waits for everything issued so far on src (an event edge the plan can replay)."""
-    if RECORDING is None:
-        dst.wait_stream(src)
-        return
-    ev = torch.cuda.Event()
-    record_event(ev, src)
-    wait_event(dst, ev)
+    """dst waits for everything issued so far on src. While recording, a private edge of the plan: its event never
+    escapes, so the plan creates and owns it natively (sdmi_plan_note_edge) and its edge pass may alias or fold it."""
+    dst.wait_stream(src)
+    if RECORDING is not None:
+        _check(_lib().sdmi_plan_note_edge(src.cuda_stream, dst.cuda_stream), "sdmi_plan_note_edge")
 
 
 class StepPlan:
@@ -111,6 +113,14 @@ class StepPlan:
         n, k = ctypes.c_int(0), ctypes.c_int(0)
         _check(_lib().sdmi_plan_info(self.handle, ctypes.byref(n), ctypes.byref(k)), "sdmi_plan_info")
         return n.value, k.value, len(self.ops)
+
+    def edge_info(self):
+        """What the edge pass made of the recorded list: dict of recorded / compiled ops, records folded into their
+        producing launch, records aliased, waits dropped, plan-owned events."""
+        v = [ctypes.c_int(0) for _ in range(6)]
+        _check(_lib().sdmi_plan_edge_info(self.handle, *[ctypes.byref(x) for x in v]), "sdmi_plan_edge_info")
+        return dict(zip(("recorded", "compiled", "folded", "aliased", "waits_dropped", "owned_events"),
+                        (x.value for x in v)))
 
     def __len__(self):
         return self.info()[0]
