@@ -21,6 +21,12 @@
 //            dkv: keys on lanes (S = Q K^T): dV^T += dO^T P, dK^T += Q^T dS
 //            dq : queries on lanes (S^T = K Q^T): dQ^T += K^T dS^T
 //            with P recomputed from the forward's log-sum-exp and delta = rowsum(dO * O).
+//
+// Shared pieces, each stated once below: wg_coords / lane_row (where a workgroup and a lane stand), row_chunks /
+// store_row (accumulator tiles to an output row), ring_tile with the streaming drivers stream_kv (forward, dQ) and
+// stream_qdo (dK/dV, fused), KeyLanes (the keys-on-lanes arithmetic of the dK/dV and fused kernels), tr_lane / tr_join
+// (the transposed LDS read behind frag_tr and frag_tr_ld), dot8 (delta) and, on the host, make_args / dispatch_dt /
+// grid_for.
 #include "common.h"
 #include "../../include/sdmi.h"
 #include <cstdlib>
@@ -30,7 +36,6 @@
 namespace {
 
 constexpr int NT = 256, ROWS = 128, TILE = 64;
-constexpr float LOG2E = 1.4426950408889634f;
 
 struct AttnArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; const bf16_t* o; const bf16_t* dout;
@@ -56,6 +61,29 @@ __device__ __forceinline__ void xcd_block(int nblk, int& blk, int& bh) {
   const int l = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (d >> 3);
   bh = l / nblk;
   blk = l - bh * nblk;
+}
+
+// Where a workgroup stands: lane and wave of the thread, row block and (batch, head) of the workgroup in the XCD-local
+// order, and the exp2 scale of a score (P = exp2(score * c - lse))
+struct WgCoords {
+  int lane, wave, blk, bh, b, h;
+  float c;
+};
+__device__ __forceinline__ WgCoords wg_coords(const AttnArgs& a) {
+  WgCoords w;
+  w.lane = threadIdx.x & 63;
+  w.wave = threadIdx.x >> 6;
+  xcd_block(a.nblk, w.blk, w.bh);
+  w.b = w.bh / a.H;
+  w.h = w.bh - w.b * a.H;
+  w.c = a.scale * kLog2e;
+  return w;
+}
+
+// the row (query or key) of 16-row group g of a wave that a lane owns: 64 * G rows per workgroup, 16 * G per wave
+template <int G>
+__device__ __forceinline__ int lane_row(int blk, int wave, int g, int lane) {
+  return blk * (64 * G) + wave * 16 * G + g * 16 + (lane & 15);
 }
 
 template <int DP> struct Tile {
@@ -108,20 +136,40 @@ __device__ __forceinline__ s16x8 frag_rows(const bf16_t* t, int rbase, int kbase
   return *(const s16x8*)(t + toff<DP>(rbase + (lane & 15), (kbase >> 3) + (lane >> 4)));
 }
 
-// transposed fragment: MFMA row = tile column (cbase + lane&15), k = tile rows permuted as
-// {rbase + 4g + j (j<4), rbase + 16 + 4g + j-4 (j>=4)} for lane group g = lane>>4 (rbase % 8 == 0, cbase % 16 == 0)
-template <int DP>
-__device__ __forceinline__ s16x8 frag_tr(const bf16_t* t, int rbase, int cbase, int lane) {
-  int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const int r = rbase + 4 * g + q, c = (cbase >> 3) + (p >> 1), w = (p & 1) * 4;
-  const bf16_t* a1 = t + toff<DP>(r, c) + w;
-  const bf16_t* a2 = t + toff<DP>(r + 16, c) + w;
+// the transposed LDS read: MFMA row = image column, k = image rows permuted as {rbase + 4g + j (j<4), rbase + 16 + 4g +
+// j-4 (j>=4)} for lane group g = lane>>4. A lane reads 4 columns (column group p = lane & 3) of rows r and r + 16
+struct TrLane {
+  int r, p;
+};
+__device__ __forceinline__ TrLane tr_lane(int rbase, int lane) {
+  return {rbase + 4 * (lane >> 4) + ((lane >> 2) & 3), lane & 3};
+}
+// a1 / a2: the lane's 8-B pieces of rows r / r + 16. The callers form the two addresses themselves: with the image's
+// address function passed in as a callable the fused kernels took 6-15 more VGPRs and attn_bwd_fused_kernel<4>, which
+// sits on the 256-VGPR ceiling, went to scratch
+__device__ __forceinline__ s16x8 tr_join(const bf16_t* a1, const bf16_t* a2) {
   s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((SDMI_LDS s16x4*)a1);
   s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((SDMI_LDS s16x4*)a2);
   s16x8 r8;
   r8[0] = lo[0]; r8[1] = lo[1]; r8[2] = lo[2]; r8[3] = lo[3];
   r8[4] = hi[0]; r8[5] = hi[1]; r8[6] = hi[2]; r8[7] = hi[3];
   return r8;
+}
+
+// transposed fragment of a swizzled tile: MFMA row = tile column (cbase + lane&15) (rbase % 8 == 0, cbase % 16 == 0)
+template <int DP>
+__device__ __forceinline__ s16x8 frag_tr(const bf16_t* t, int rbase, int cbase, int lane) {
+  const TrLane l = tr_lane(rbase, lane);
+  const int c = (cbase >> 3) + (l.p >> 1), w = (l.p & 1) * 4;
+  return tr_join(t + toff<DP>(l.r, c) + w, t + toff<DP>(l.r + 16, c) + w);
+}
+
+// the same of a plain row-major image with LD-element rows
+template <int LD>
+__device__ __forceinline__ s16x8 frag_tr_ld(const bf16_t* t, int rbase, int cbase, int lane) {
+  const TrLane l = tr_lane(rbase, lane);
+  const bf16_t* a1 = t + l.r * LD + cbase + 4 * l.p;
+  return tr_join(a1, a1 + 16 * LD);
 }
 
 // B-operand fragment from two accumulator tiles (rows = k): elements j<4 from a[j], j>=4 from b[j-4]
@@ -156,6 +204,33 @@ __device__ __forceinline__ void store4(bf16_t* dst, const f32x4& v, float s) {
   w.x = pack2bf(v[0] * s, v[1] * s);
   w.y = pack2bf(v[2] * s, v[3] * s);
   *(uint2*)dst = w;
+}
+
+// the live 4-column chunks of the output row a lane holds in DT accumulator tiles: f(t, d0) for tile t at columns d0 ..
+// d0 + 3 of the head, d0 < d
+template <int DT, class F>
+__device__ __forceinline__ void row_chunks(int d, int lane, F f) {
+#pragma unroll
+  for (int t = 0; t < DT; ++t) {
+    const int d0 = 16 * t + (lane >> 4) * 4;
+    if (d0 < d) f(t, d0);
+  }
+}
+
+// accumulator tiles -> one bf16 output row (dst: column 0 of the head in that row), scaled by s
+template <int DT>
+__device__ __forceinline__ void store_row(bf16_t* dst, const f32x4 (&acc)[DT], int d, float s, int lane) {
+  row_chunks<DT>(d, lane, [&](int t, int d0) __attribute__((always_inline)) { store4(dst + d0, acc[t], s); });
+}
+
+// acc + sum of the 8 products of two bf16 chunks, in element order (delta = rowsum(dO * O))
+__device__ __forceinline__ float dot8(const uint4& u, const uint4& v, float acc) {
+  float x[8], y[8];
+  unpack8(u, x);
+  unpack8(v, y);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc = fmaf(x[e], y[e], acc);
+  return acc;
 }
 
 // max / sum over the four lanes l, l^16, l^32, l^48 (the four 4-key row groups of one query column):
@@ -199,41 +274,29 @@ using Full = std::false_type;
 using Ragged = std::true_type;
 
 // =============================================================================================
-// forward
+// the double-buffered LDS ring of two 64-row tiles per buffer: smem is [buf][first | second tile]
 // =============================================================================================
+template <int DP>
+__device__ __forceinline__ bf16_t* ring_tile(bf16_t* smem, int buf, int second) {
+  return smem + (buf * 2 + second) * Tile<DP>::ELEMS;
+}
+
+// K | V ring (forward, dQ): streams the key tiles of head w.h through smem and calls body(sK, sV, k0, Full{} | Ragged{})
+// once per 64-key tile -- the next tile is prefetched into registers while the current one is consumed, one barrier per
+// tile. Ragged: the last key tile of an S that is no multiple of 64 (cross-attention S = 77), whose keys >= S the body
+// must leave out.
 // ONES (d % 16 == 8: the last output tile has free padded columns): column d of every valid V row is 1, so the
 // PV MFMA accumulates the softmax row sum into o[g][DT-1] (tile row 8: lane group 2, element 0) -- no per-score
 // VALU row-sum adds in the loop; the sum is of the bf16 P the MFMA consumes, i.e. exactly what O accumulated
-template <int DT, bool ONES>
-__global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnArgs a) {
-  constexpr int DP = Dim<DT>::DP, KS = Dim<DT>::KS;
-  __shared__ __attribute__((aligned(16))) bf16_t smem[4 * Tile<DP>::ELEMS];  // [buf][K|V]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int blk, bh;
-  xcd_block(a.nblk, blk, bh);
-  const int b = bh / a.H, h = bh - b * a.H;
-  const float c = a.scale * LOG2E;
-  const bf16_t* Q = a.q + (long long)b * a.N * a.ldq;
-  const bf16_t* K = a.k + (long long)b * a.S * a.ldk;
-  const bf16_t* V = a.v + (long long)b * a.S * a.ldv;
-
-  int myq[2];
-  s16x8 qf[2][KS];
-  float m[2], l[2];
-  f32x4 o[2][DT];
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    myq[g] = blk * ROWS + wave * 32 + g * 16 + (lane & 15);
-    row_frags<DP>(qf[g], Q, a.ldq, myq[g], a.N, h * a.d, a.d, lane);
-    m[g] = -INFINITY;
-    l[g] = 0.f;
-#pragma unroll
-    for (int t = 0; t < DT; ++t) o[g][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
+template <int DP, bool ONES, class Body>
+__device__ __forceinline__ void stream_kv(bf16_t* smem, const AttnArgs& a, const WgCoords& w, Body body) {
+  const bf16_t* K = a.k + (long long)w.b * a.S * a.ldk;
+  const bf16_t* V = a.v + (long long)w.b * a.S * a.ldv;
   uint4 rk[Tile<DP>::CPT], rv[Tile<DP>::CPT];
-  // ONES: the 8-column chunk of V starting at column d (all padding) becomes {1, 0, ..., 0} on valid key rows
-  auto fetch_v = [&](int row0) __attribute__((always_inline)) {
-    tile_fetch<DP>(rv, V, a.ldv, row0, a.S, h * a.d, a.d);
+  auto fetch = [&](int row0) __attribute__((always_inline)) {
+    tile_fetch<DP>(rk, K, a.ldk, row0, a.S, w.h * a.d, a.d);
+    tile_fetch<DP>(rv, V, a.ldv, row0, a.S, w.h * a.d, a.d);
+    // ONES: the 8-column chunk of V starting at column d (all padding) becomes {1, 0, ..., 0} on valid key rows
     if constexpr (ONES) {
       constexpr int CPR = DP / 8;
 #pragma unroll
@@ -243,20 +306,92 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnArgs a) {
       }
     }
   };
-  tile_fetch<DP>(rk, K, a.ldk, 0, a.S, h * a.d, a.d);
-  fetch_v(0);
-  tile_store<DP>(smem, rk);
-  tile_store<DP>(smem + Tile<DP>::ELEMS, rv);
+  auto put = [&](int buf) __attribute__((always_inline)) {
+    tile_store<DP>(ring_tile<DP>(smem, buf, 0), rk);
+    tile_store<DP>(ring_tile<DP>(smem, buf, 1), rv);
+  };
+  fetch(0);
+  put(0);
   __syncthreads();
   int cur = 0;
   auto step = [&](int k0, auto rag) __attribute__((always_inline)) {
     const bool more = k0 + TILE < a.S;
-    if (more) {
-      tile_fetch<DP>(rk, K, a.ldk, k0 + TILE, a.S, h * a.d, a.d);
-      fetch_v(k0 + TILE);
+    if (more) fetch(k0 + TILE);
+    body(ring_tile<DP>(smem, cur, 0), ring_tile<DP>(smem, cur, 1), k0, rag);
+    if (more) put(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  };
+  int k0 = 0;
+  for (; k0 + TILE <= a.S; k0 += TILE) step(k0, Full{});
+  if (k0 < a.S) step(k0, Ragged{});
+}
+
+// Q | dO ring with the tile's -lse | -delta in sLD[buf] (dK/dV, fused): streams the query tiles of head w.h and calls
+// body(sQ, sO, sLD[buf], q0) once per 64-query tile; rows >= N are zero with -lse = -inf (p = 0)
+template <int DP, class Body>
+__device__ __forceinline__ void stream_qdo(bf16_t* smem, float (&sLD)[2][2][64], const AttnArgs& a, const WgCoords& w,
+                                           Body body) {
+  const bf16_t* Q = a.q + (long long)w.b * a.N * a.ldq;
+  const bf16_t* dO = a.dout + (long long)w.b * a.N * a.lddo;
+  uint4 rq[Tile<DP>::CPT], ro[Tile<DP>::CPT];
+  float rl = 0.f, rd = 0.f;
+  auto fetch = [&](int q0) __attribute__((always_inline)) {
+    tile_fetch<DP>(rq, Q, a.ldq, q0, a.N, w.h * a.d, a.d);
+    tile_fetch<DP>(ro, dO, a.lddo, q0, a.N, w.h * a.d, a.d);
+    if (threadIdx.x < 64) {
+      int q = q0 + threadIdx.x;
+      rl = q < a.N ? -a.lse[(long long)w.bh * a.N + q] : -INFINITY;  // invalid rows: p = 0
+      rd = q < a.N ? -a.delta[(long long)w.bh * a.N + q] : 0.f;
     }
-    const bf16_t* sK = smem + cur * 2 * Tile<DP>::ELEMS;
-    const bf16_t* sV = sK + Tile<DP>::ELEMS;
+  };
+  auto put = [&](int buf) __attribute__((always_inline)) {
+    tile_store<DP>(ring_tile<DP>(smem, buf, 0), rq);
+    tile_store<DP>(ring_tile<DP>(smem, buf, 1), ro);
+    if (threadIdx.x < 64) {
+      sLD[buf][0][threadIdx.x] = rl;
+      sLD[buf][1][threadIdx.x] = rd;
+    }
+  };
+  fetch(0);
+  put(0);
+  __syncthreads();
+  int cur = 0;
+  for (int q0 = 0; q0 < a.N; q0 += TILE) {
+    const bool more = q0 + TILE < a.N;
+    if (more) fetch(q0 + TILE);
+    body(ring_tile<DP>(smem, cur, 0), ring_tile<DP>(smem, cur, 1), sLD[cur], q0);
+    if (more) put(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+
+// =============================================================================================
+// forward
+// =============================================================================================
+template <int DT, bool ONES>
+__global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnArgs a) {
+  constexpr int DP = Dim<DT>::DP, KS = Dim<DT>::KS;
+  __shared__ __attribute__((aligned(16))) bf16_t smem[4 * Tile<DP>::ELEMS];  // [buf][K|V]
+  const WgCoords w = wg_coords(a);
+  const int lane = w.lane;
+  const float c = w.c;
+
+  int myq[2];
+  s16x8 qf[2][KS];
+  float m[2], l[2];
+  f32x4 o[2][DT];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    myq[g] = lane_row<2>(w.blk, w.wave, g, lane);
+    row_frags<DP>(qf[g], a.q + (long long)w.b * a.N * a.ldq, a.ldq, myq[g], a.N, w.h * a.d, a.d, lane);
+    m[g] = -INFINITY;
+    l[g] = 0.f;
+#pragma unroll
+    for (int t = 0; t < DT; ++t) o[g][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  stream_kv<DP, ONES>(smem, a, w, [&](const bf16_t* sK, const bf16_t* sV, int k0, auto rag) __attribute__((always_inline)) {
     f32x4 s[2][4];
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
@@ -268,7 +403,7 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnArgs a) {
         s[1][kb] = mfma(kf, qf[1][ks], s[1][kb]);
       }
     }
-    if constexpr (decltype(rag)::value) {  // last key tile of a ragged S (cross-attention S = 77): keys >= S out
+    if constexpr (decltype(rag)::value) {  // keys >= S out
       const int lim = a.S - k0 - (lane >> 4) * 4;
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb)
@@ -316,33 +451,95 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnArgs a) {
         o[0][t] = mfma(vf, pf[0][s2], o[0][t]);
         o[1][t] = mfma(vf, pf[1][s2], o[1][t]);
       }
-    if (more) {
-      bf16_t* nK = smem + (cur ^ 1) * 2 * Tile<DP>::ELEMS;
-      tile_store<DP>(nK, rk);
-      tile_store<DP>(nK + Tile<DP>::ELEMS, rv);
-    }
-    __syncthreads();
-    cur ^= 1;
-  };
-  int k0 = 0;
-  for (; k0 + TILE <= a.S; k0 += TILE) step(k0, Full{});
-  if (k0 < a.S) step(k0, Ragged{});
+  });
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
     // ONES: the row sum sits in lane group 2 of the last output tile; every lane of the query column takes it
     const float lt = ONES ? __shfl(o[g][DT - 1][0], 32 + (lane & 15)) : xsum4(l[g]);
     if (myq[g] < a.N) {
-      const float inv = 1.f / lt;
-      bf16_t* O = a.out + ((long long)b * a.N + myq[g]) * a.ldo + h * a.d;
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        int d0 = 16 * t + (lane >> 4) * 4;
-        if (d0 < a.d) store4(O + d0, o[g][t], inv);
-      }
-      if ((lane >> 4) == 0) a.lse[(long long)bh * a.N + myq[g]] = m[g] + __log2f(lt);
+      store_row<DT>(a.out + ((long long)w.b * a.N + myq[g]) * a.ldo + w.h * a.d, o[g], a.d, 1.f / lt, lane);
+      if ((lane >> 4) == 0) a.lse[(long long)w.bh * a.N + myq[g]] = m[g] + __log2f(lt);
     }
   }
 }
+
+// =============================================================================================
+// keys on lanes (S = Q K^T), shared by the dK/dV and the fused backward: G 16-key groups per wave hold their K and V
+// rows as MFMA fragments and accumulate dV^T += dO^T P, dK^T += Q^T dS over the streamed query tiles
+// =============================================================================================
+template <int DT, int G>
+struct KeyLanes {
+  static constexpr int DP = Dim<DT>::DP, KS = Dim<DT>::KS;
+  int key[G];
+  s16x8 kf[G][KS], vf[G][KS];
+  f32x4 dk[G][DT], dv[G][DT];
+
+  __device__ __forceinline__ void init(const AttnArgs& a, const WgCoords& w) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      key[g] = lane_row<G>(w.blk, w.wave, g, w.lane);
+      row_frags<DP>(kf[g], a.k + (long long)w.b * a.S * a.ldk, a.ldk, key[g], a.S, w.h * a.d, a.d, w.lane);
+      row_frags<DP>(vf[g], a.v + (long long)w.b * a.S * a.ldv, a.ldv, key[g], a.S, w.h * a.d, a.d, w.lane);
+#pragma unroll
+      for (int t = 0; t < DT; ++t) dk[g][t] = dv[g][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  }
+
+  // P and dS = P (dP - delta) of the G key groups against the 16 queries qb * 16 .. +15 of the tile
+  __device__ __forceinline__ void p_ds_block(f32x4 (&p)[G], f32x4 (&ds)[G], const bf16_t* sQ, const bf16_t* sO,
+                                             const float (&nLD)[2][64], int qb, const WgCoords& w) const {
+    const int qi = qb * 16 + (w.lane >> 4) * 4;
+    const f32x4 nL = *(const f32x4*)&nLD[0][qi], nD = *(const f32x4*)&nLD[1][qi];
+    // dP accumulates on top of -delta: the MFMA yields dP - delta directly (no per-element subtraction)
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      p[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      ds[g] = nD;
+    }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      s16x8 qa = frag_rows<DP>(sQ, qb * 16, ks * 32, w.lane);
+      s16x8 oa = frag_rows<DP>(sO, qb * 16, ks * 32, w.lane);
+#pragma unroll
+      for (int g = 0; g < G; ++g) p[g] = mfma(qa, kf[g][ks], p[g]);
+#pragma unroll
+      for (int g = 0; g < G; ++g) ds[g] = mfma(oa, vf[g][ks], ds[g]);
+    }
+    const float nl[4] = {nL[0], nL[1], nL[2], nL[3]};
+#pragma unroll
+    for (int g = 0; g < G; ++g) p_ds(p[g], ds[g], w.c, nl);
+  }
+
+  // dV += dO^T P, dK += Q^T dS over the 32 queries 32 * s2 .. +31 of the tile (two 16-query blocks of p_ds_block)
+  __device__ __forceinline__ void accumulate(const bf16_t* sQ, const bf16_t* sO, int s2, const f32x4 (&p0)[G],
+                                             const f32x4 (&p1)[G], const f32x4 (&ds0)[G], const f32x4 (&ds1)[G],
+                                             int lane) {
+    s16x8 pf[G], df[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      pf[g] = pack_acc(p0[g], p1[g]);
+      df[g] = pack_acc(ds0[g], ds1[g]);
+    }
+#pragma unroll
+    for (int t = 0; t < DT; ++t) {
+      s16x8 ot = frag_tr<DP>(sO, 32 * s2, 16 * t, lane);
+#pragma unroll
+      for (int g = 0; g < G; ++g) dv[g][t] = mfma(ot, pf[g], dv[g][t]);
+      s16x8 qt = frag_tr<DP>(sQ, 32 * s2, 16 * t, lane);
+#pragma unroll
+      for (int g = 0; g < G; ++g) dk[g][t] = mfma(qt, df[g], dk[g][t]);
+    }
+  }
+
+  __device__ __forceinline__ void store(const AttnArgs& a, const WgCoords& w) const {
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+      if (key[g] < a.S) {
+        store_row<DT>(a.dk + ((long long)w.b * a.S + key[g]) * a.lddk + w.h * a.d, dk[g], a.d, a.scale, w.lane);
+        store_row<DT>(a.dv + ((long long)w.b * a.S + key[g]) * a.lddv + w.h * a.d, dv[g], a.d, 1.f, w.lane);
+      }
+  }
+};
 
 // =============================================================================================
 // backward: dK, dV (keys on lanes, 128 keys per workgroup, query tiles streamed)
@@ -351,118 +548,23 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnArgs a) {
 // the keys). The query tile is consumed in two 32-query halves so the live P / dS accumulators stay at G x 2.
 template <int DT, int G = 2>
 __global__ __launch_bounds__(NT, 2) void attn_bwd_dkv_kernel(AttnArgs a) {
-  constexpr int DP = Dim<DT>::DP, KS = Dim<DT>::KS;
+  constexpr int DP = Dim<DT>::DP;
   __shared__ __attribute__((aligned(16))) bf16_t smem[4 * Tile<DP>::ELEMS];  // [buf][Q|dO]
   __shared__ __attribute__((aligned(16))) float sLD[2][2][64];               // [buf][-lse|-delta]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int blk, bh;
-  xcd_block(a.nblk, blk, bh);
-  const int b = bh / a.H, h = bh - b * a.H;
-  const float c = a.scale * LOG2E;
-  const bf16_t* Q = a.q + (long long)b * a.N * a.ldq;
-  const bf16_t* dO = a.dout + (long long)b * a.N * a.lddo;
-
-  int mykey[G];
-  s16x8 kf[G][KS], vf[G][KS];
-  f32x4 dk[G][DT], dv[G][DT];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    mykey[g] = blk * (64 * G) + wave * 16 * G + g * 16 + (lane & 15);
-    row_frags<DP>(kf[g], a.k + (long long)b * a.S * a.ldk, a.ldk, mykey[g], a.S, h * a.d, a.d, lane);
-    row_frags<DP>(vf[g], a.v + (long long)b * a.S * a.ldv, a.ldv, mykey[g], a.S, h * a.d, a.d, lane);
-#pragma unroll
-    for (int t = 0; t < DT; ++t) dk[g][t] = dv[g][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-
-  uint4 rq[Tile<DP>::CPT], ro[Tile<DP>::CPT];
-  float rl = 0.f, rd = 0.f;
-  auto fetch = [&](int q0) __attribute__((always_inline)) {
-    tile_fetch<DP>(rq, Q, a.ldq, q0, a.N, h * a.d, a.d);
-    tile_fetch<DP>(ro, dO, a.lddo, q0, a.N, h * a.d, a.d);
-    if (threadIdx.x < 64) {
-      int q = q0 + threadIdx.x;
-      rl = q < a.N ? -a.lse[(long long)bh * a.N + q] : -INFINITY;  // invalid rows: p = 0
-      rd = q < a.N ? -a.delta[(long long)bh * a.N + q] : 0.f;
-    }
-  };
-  auto put = [&](int buf) __attribute__((always_inline)) {
-    tile_store<DP>(smem + buf * 2 * Tile<DP>::ELEMS, rq);
-    tile_store<DP>(smem + buf * 2 * Tile<DP>::ELEMS + Tile<DP>::ELEMS, ro);
-    if (threadIdx.x < 64) {
-      sLD[buf][0][threadIdx.x] = rl;
-      sLD[buf][1][threadIdx.x] = rd;
-    }
-  };
-  fetch(0);
-  put(0);
-  __syncthreads();
-  int cur = 0;
-  for (int q0 = 0; q0 < a.N; q0 += TILE) {
-    const bool more = q0 + TILE < a.N;
-    if (more) fetch(q0 + TILE);
-    const bf16_t* sQ = smem + cur * 2 * Tile<DP>::ELEMS;
-    const bf16_t* sO = sQ + Tile<DP>::ELEMS;
+  const WgCoords w = wg_coords(a);
+  KeyLanes<DT, G> kl;
+  kl.init(a, w);
+  stream_qdo<DP>(smem, sLD, a, w,
+                 [&](const bf16_t* sQ, const bf16_t* sO, const float (&nLD)[2][64], int) __attribute__((always_inline)) {
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {  // query rows 32*s2 .. +32 of the tile
-      f32x4 p[G][2], ds[G][2];
+      f32x4 p[2][G], ds[2][G];
 #pragma unroll
-      for (int h2 = 0; h2 < 2; ++h2) {
-        const int qb = 2 * s2 + h2;
-        const int qi = qb * 16 + (lane >> 4) * 4;
-        const f32x4 nL = *(const f32x4*)&sLD[cur][0][qi], nD = *(const f32x4*)&sLD[cur][1][qi];
-        // dP accumulates on top of -delta: the MFMA yields dP - delta directly (no per-element subtraction)
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          p[g][h2] = (f32x4){0.f, 0.f, 0.f, 0.f};
-          ds[g][h2] = nD;
-        }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          s16x8 qa = frag_rows<DP>(sQ, qb * 16, ks * 32, lane);
-          s16x8 oa = frag_rows<DP>(sO, qb * 16, ks * 32, lane);
-#pragma unroll
-          for (int g = 0; g < G; ++g) p[g][h2] = mfma(qa, kf[g][ks], p[g][h2]);
-#pragma unroll
-          for (int g = 0; g < G; ++g) ds[g][h2] = mfma(oa, vf[g][ks], ds[g][h2]);
-        }
-        const float nl[4] = {nL[0], nL[1], nL[2], nL[3]};
-#pragma unroll
-        for (int g = 0; g < G; ++g) p_ds(p[g][h2], ds[g][h2], c, nl);
-      }
-      s16x8 pf[G], df[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        pf[g] = pack_acc(p[g][0], p[g][1]);
-        df[g] = pack_acc(ds[g][0], ds[g][1]);
-      }
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        s16x8 ot = frag_tr<DP>(sO, 32 * s2, 16 * t, lane);
-#pragma unroll
-        for (int g = 0; g < G; ++g) dv[g][t] = mfma(ot, pf[g], dv[g][t]);
-        s16x8 qt = frag_tr<DP>(sQ, 32 * s2, 16 * t, lane);
-#pragma unroll
-        for (int g = 0; g < G; ++g) dk[g][t] = mfma(qt, df[g], dk[g][t]);
-      }
+      for (int h2 = 0; h2 < 2; ++h2) kl.p_ds_block(p[h2], ds[h2], sQ, sO, nLD, 2 * s2 + h2, w);
+      kl.accumulate(sQ, sO, s2, p[0], p[1], ds[0], ds[1], w.lane);
     }
-    if (more) put(cur ^ 1);
-    __syncthreads();
-    cur ^= 1;
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-    if (mykey[g] < a.S) {
-      bf16_t* DK = a.dk + ((long long)b * a.S + mykey[g]) * a.lddk + h * a.d;
-      bf16_t* DV = a.dv + ((long long)b * a.S + mykey[g]) * a.lddv + h * a.d;
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        int d0 = 16 * t + (lane >> 4) * 4;
-        if (d0 < a.d) {
-          store4(DK + d0, dk[g][t], a.scale);
-          store4(DV + d0, dv[g][t], 1.f);
-        }
-      }
-    }
+  });
+  kl.store(a, w);
 }
 
 // =============================================================================================
@@ -472,13 +574,9 @@ template <int DT, int G = 2>
 __global__ __launch_bounds__(NT, 2) void attn_bwd_dq_kernel(AttnArgs a) {
   constexpr int DP = Dim<DT>::DP, KS = Dim<DT>::KS;
   __shared__ __attribute__((aligned(16))) bf16_t smem[4 * Tile<DP>::ELEMS];  // [buf][K|V]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int blk, bh;
-  xcd_block(a.nblk, blk, bh);
-  const int b = bh / a.H, h = bh - b * a.H;
-  const float c = a.scale * LOG2E;
-  const bf16_t* K = a.k + (long long)b * a.S * a.ldk;
-  const bf16_t* V = a.v + (long long)b * a.S * a.ldv;
+  const WgCoords w = wg_coords(a);
+  const int lane = w.lane;
+  const float c = w.c;
 
   int myq[G];
   s16x8 qf[G][KS], of[G][KS];
@@ -486,26 +584,21 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_dq_kernel(AttnArgs a) {
   f32x4 dq[G][DT];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    myq[g] = blk * (64 * G) + wave * 16 * G + g * 16 + (lane & 15);
-    row_frags<DP>(qf[g], a.q + (long long)b * a.N * a.ldq, a.ldq, myq[g], a.N, h * a.d, a.d, lane);
-    row_frags<DP>(of[g], a.dout + (long long)b * a.N * a.lddo, a.lddo, myq[g], a.N, h * a.d, a.d, lane);
+    myq[g] = lane_row<G>(w.blk, w.wave, g, lane);
+    row_frags<DP>(qf[g], a.q + (long long)w.b * a.N * a.ldq, a.ldq, myq[g], a.N, w.h * a.d, a.d, lane);
+    row_frags<DP>(of[g], a.dout + (long long)w.b * a.N * a.lddo, a.lddo, myq[g], a.N, w.h * a.d, a.d, lane);
     const bool ok = myq[g] < a.N;
-    const float L = ok ? -a.lse[(long long)bh * a.N + myq[g]] : -INFINITY;
+    const float L = ok ? -a.lse[(long long)w.bh * a.N + myq[g]] : -INFINITY;
     // delta = rowsum(dO * O) of this query row: the four lane groups hold disjoint 8-column chunks of the row
     float D = 0.f;
     {
       s16x8 orow[KS];
-      row_frags<DP>(orow, a.o + (long long)b * a.N * a.ldo, a.ldo, myq[g], a.N, h * a.d, a.d, lane);
+      row_frags<DP>(orow, a.o + (long long)w.b * a.N * a.ldo, a.ldo, myq[g], a.N, w.h * a.d, a.d, lane);
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        float x[8], y[8];
-        unpack8(__builtin_bit_cast(uint4, orow[ks]), x);
-        unpack8(__builtin_bit_cast(uint4, of[g][ks]), y);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) D = fmaf(x[e], y[e], D);
-      }
+      for (int ks = 0; ks < KS; ++ks)
+        D = dot8(__builtin_bit_cast(uint4, orow[ks]), __builtin_bit_cast(uint4, of[g][ks]), D);
       D = xsum4(D);
-      if (ok && (lane >> 4) == 0) ((float*)a.delta)[(long long)bh * a.N + myq[g]] = D;
+      if (ok && (lane >> 4) == 0) ((float*)a.delta)[(long long)w.bh * a.N + myq[g]] = D;
       D = -D;
     }
     nlse[g] = L;
@@ -513,21 +606,7 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_dq_kernel(AttnArgs a) {
 #pragma unroll
     for (int t = 0; t < DT; ++t) dq[g][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
-  uint4 rk[Tile<DP>::CPT], rv[Tile<DP>::CPT];
-  tile_fetch<DP>(rk, K, a.ldk, 0, a.S, h * a.d, a.d);
-  tile_fetch<DP>(rv, V, a.ldv, 0, a.S, h * a.d, a.d);
-  tile_store<DP>(smem, rk);
-  tile_store<DP>(smem + Tile<DP>::ELEMS, rv);
-  __syncthreads();
-  int cur = 0;
-  auto step = [&](int k0, auto rag) __attribute__((always_inline)) {
-    const bool more = k0 + TILE < a.S;
-    if (more) {
-      tile_fetch<DP>(rk, K, a.ldk, k0 + TILE, a.S, h * a.d, a.d);
-      tile_fetch<DP>(rv, V, a.ldv, k0 + TILE, a.S, h * a.d, a.d);
-    }
-    const bf16_t* sK = smem + cur * 2 * Tile<DP>::ELEMS;
-    const bf16_t* sV = sK + Tile<DP>::ELEMS;
+  stream_kv<DP, false>(smem, a, w, [&](const bf16_t* sK, const bf16_t* sV, int k0, auto rag) __attribute__((always_inline)) {
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {  // keys 32*s2 .. +32 of the tile
       f32x4 ds[G][2];
@@ -574,27 +653,11 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_dq_kernel(AttnArgs a) {
         for (int g = 0; g < G; ++g) dq[g][t] = mfma(kt, df[g], dq[g][t]);
       }
     }
-    if (more) {
-      bf16_t* nK = smem + (cur ^ 1) * 2 * Tile<DP>::ELEMS;
-      tile_store<DP>(nK, rk);
-      tile_store<DP>(nK + Tile<DP>::ELEMS, rv);
-    }
-    __syncthreads();
-    cur ^= 1;
-  };
-  int k0 = 0;
-  for (; k0 + TILE <= a.S; k0 += TILE) step(k0, Full{});
-  if (k0 < a.S) step(k0, Ragged{});
+  });
 #pragma unroll
   for (int g = 0; g < G; ++g)
-    if (myq[g] < a.N) {
-      bf16_t* DQ = a.dq + ((long long)b * a.N + myq[g]) * a.lddq + h * a.d;
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        int d0 = 16 * t + (lane >> 4) * 4;
-        if (d0 < a.d) store4(DQ + d0, dq[g][t], a.scale);
-      }
-    }
+    if (myq[g] < a.N)
+      store_row<DT>(a.dq + ((long long)w.b * a.N + myq[g]) * a.lddq + w.h * a.d, dq[g], a.d, a.scale, lane);
 }
 
 // =============================================================================================
@@ -612,134 +675,49 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_dq_kernel(AttnArgs a) {
 // =============================================================================================
 constexpr int LDQ = TILE + 8;  // dS^T image row: 64 queries + 16 B of padding
 
-template <int LD>
-__device__ __forceinline__ s16x8 frag_tr_ld(const bf16_t* t, int rbase, int cbase, int lane) {
-  int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const bf16_t* a1 = t + (rbase + 4 * g + q) * LD + cbase + 4 * p;
-  const bf16_t* a2 = a1 + 16 * LD;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((SDMI_LDS s16x4*)a1);
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((SDMI_LDS s16x4*)a2);
-  s16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
-}
-
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 constexpr int ATTN_CPOL_SC1 = 16;  // buffer cache policy: device (agent) scope coherence
 
 template <int DT>
 __global__ __launch_bounds__(NT, 2) void attn_bwd_fused_kernel(AttnArgs a) {
-  constexpr int DP = Dim<DT>::DP, KS = Dim<DT>::KS;
+  constexpr int DP = Dim<DT>::DP;
   constexpr int LDK = Tile<DP>::LD;
   __shared__ __attribute__((aligned(16))) bf16_t smem[4 * Tile<DP>::ELEMS];  // [buf][Q|dO]
   __shared__ __attribute__((aligned(16))) bf16_t sK[ROWS * LDK];             // this workgroup's key block
   __shared__ __attribute__((aligned(16))) bf16_t sDS[ROWS * LDQ];            // dS^T of the current query tile
   __shared__ __attribute__((aligned(16))) float sLD[2][2][64];               // [buf][-lse|-delta]
   __shared__ int sflag;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int kb, bh;
-  xcd_block(a.nblk, kb, bh);
-  const int b = bh / a.H, h = bh - b * a.H;
+  const WgCoords w = wg_coords(a);  // w.blk: the key block
+  const int lane = w.lane, wave = w.wave, bh = w.bh;
   const int nkb = a.nblk;
-  const float c = a.scale * LOG2E;
-  const bf16_t* Q = a.q + (long long)b * a.N * a.ldq;
-  const bf16_t* dO = a.dout + (long long)b * a.N * a.lddo;
-  const bf16_t* Kb = a.k + (long long)b * a.S * a.ldk;
 
   {  // the workgroup's 128 keys (rows >= S zero) for the dQ products
     uint4 rk[Tile<DP>::CPT];
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      tile_fetch<DP>(rk, Kb, a.ldk, kb * ROWS + half * TILE, a.S, h * a.d, a.d);
+      tile_fetch<DP>(rk, a.k + (long long)w.b * a.S * a.ldk, a.ldk, w.blk * ROWS + half * TILE, a.S, w.h * a.d, a.d);
       tile_store<DP>(sK + half * Tile<DP>::ELEMS, rk);
     }
   }
-  int mykey[2];
-  bool kok[2];
-  s16x8 kf[2][KS], vf[2][KS];
-  f32x4 dk[2][DT], dv[2][DT];
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    mykey[g] = kb * ROWS + wave * 32 + g * 16 + (lane & 15);
-    kok[g] = mykey[g] < a.S;
-    row_frags<DP>(kf[g], Kb, a.ldk, mykey[g], a.S, h * a.d, a.d, lane);
-    row_frags<DP>(vf[g], a.v + (long long)b * a.S * a.ldv, a.ldv, mykey[g], a.S, h * a.d, a.d, lane);
-#pragma unroll
-    for (int t = 0; t < DT; ++t) dk[g][t] = dv[g][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-
-  uint4 rq[Tile<DP>::CPT], ro[Tile<DP>::CPT];
-  float rl = 0.f, rd = 0.f;
-  auto fetch = [&](int q0) __attribute__((always_inline)) {
-    tile_fetch<DP>(rq, Q, a.ldq, q0, a.N, h * a.d, a.d);
-    tile_fetch<DP>(ro, dO, a.lddo, q0, a.N, h * a.d, a.d);
-    if (threadIdx.x < 64) {
-      int q = q0 + threadIdx.x;
-      rl = q < a.N ? -a.lse[(long long)bh * a.N + q] : -INFINITY;  // invalid rows: p = 0
-      rd = q < a.N ? -a.delta[(long long)bh * a.N + q] : 0.f;
-    }
-  };
-  auto put = [&](int buf) __attribute__((always_inline)) {
-    tile_store<DP>(smem + buf * 2 * Tile<DP>::ELEMS, rq);
-    tile_store<DP>(smem + buf * 2 * Tile<DP>::ELEMS + Tile<DP>::ELEMS, ro);
-    if (threadIdx.x < 64) {
-      sLD[buf][0][threadIdx.x] = rl;
-      sLD[buf][1][threadIdx.x] = rd;
-    }
-  };
+  KeyLanes<DT, 2> kl;
+  kl.init(a, w);
+  const bool kok[2] = {kl.key[0] < a.S, kl.key[1] < a.S};
   const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc((void*)a.dq_part, (short)0, 0x7fffffff, 0x00020000);
   const int ntq = (a.N + TILE - 1) / TILE;
-  fetch(0);
-  put(0);
-  __syncthreads();
-  int cur = 0;
-  for (int q0 = 0; q0 < a.N; q0 += TILE) {
-    const bool more = q0 + TILE < a.N;
-    if (more) fetch(q0 + TILE);
-    const bf16_t* sQ = smem + cur * 2 * Tile<DP>::ELEMS;
-    const bf16_t* sO = sQ + Tile<DP>::ELEMS;
-    f32x4 p[2][4], ds[2][4];
+  stream_qdo<DP>(smem, sLD, a, w,
+                 [&](const bf16_t* sQ, const bf16_t* sO, const float (&nLD)[2][64], int q0) __attribute__((always_inline)) {
+    f32x4 p[4][2], ds[4][2];
 #pragma unroll
     for (int qb = 0; qb < 4; ++qb) {
-      const int qi = qb * 16 + (lane >> 4) * 4;
-      const f32x4 nL = *(const f32x4*)&sLD[cur][0][qi], nD = *(const f32x4*)&sLD[cur][1][qi];
-      p[0][qb] = p[1][qb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      ds[0][qb] = ds[1][qb] = nD;  // dP accumulates on top of -delta
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        s16x8 qa = frag_rows<DP>(sQ, qb * 16, ks * 32, lane);
-        s16x8 oa = frag_rows<DP>(sO, qb * 16, ks * 32, lane);
-        p[0][qb] = mfma(qa, kf[0][ks], p[0][qb]);
-        p[1][qb] = mfma(qa, kf[1][ks], p[1][qb]);
-        ds[0][qb] = mfma(oa, vf[0][ks], ds[0][qb]);
-        ds[1][qb] = mfma(oa, vf[1][ks], ds[1][qb]);
-      }
-      const float nl[4] = {nL[0], nL[1], nL[2], nL[3]};
+      kl.p_ds_block(p[qb], ds[qb], sQ, sO, nLD, qb, w);
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
-        p_ds(p[g][qb], ds[g][qb], c, nl);
-        if (!kok[g]) p[g][qb] = ds[g][qb] = (f32x4){0.f, 0.f, 0.f, 0.f};  // keys >= S (zero K rows) must not reach dQ
-        uint2 w;
-        w.x = pack2bf(ds[g][qb][0], ds[g][qb][1]);
-        w.y = pack2bf(ds[g][qb][2], ds[g][qb][3]);
-        *(uint2*)(sDS + (wave * 32 + g * 16 + (lane & 15)) * LDQ + qb * 16 + (lane >> 4) * 4) = w;
+        if (!kok[g]) p[qb][g] = ds[qb][g] = (f32x4){0.f, 0.f, 0.f, 0.f};  // keys >= S (zero K rows) must not reach dQ
+        store4(sDS + (wave * 32 + g * 16 + (lane & 15)) * LDQ + qb * 16 + (lane >> 4) * 4, ds[qb][g], 1.f);
       }
     }
 #pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      s16x8 pf0 = pack_acc(p[0][2 * s2], p[0][2 * s2 + 1]), pf1 = pack_acc(p[1][2 * s2], p[1][2 * s2 + 1]);
-      s16x8 df0 = pack_acc(ds[0][2 * s2], ds[0][2 * s2 + 1]), df1 = pack_acc(ds[1][2 * s2], ds[1][2 * s2 + 1]);
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        s16x8 ot = frag_tr<DP>(sO, 32 * s2, 16 * t, lane);
-        dv[0][t] = mfma(ot, pf0, dv[0][t]);
-        dv[1][t] = mfma(ot, pf1, dv[1][t]);
-        s16x8 qt = frag_tr<DP>(sQ, 32 * s2, 16 * t, lane);
-        dk[0][t] = mfma(qt, df0, dk[0][t]);
-        dk[1][t] = mfma(qt, df1, dk[1][t]);
-      }
-    }
+    for (int s2 = 0; s2 < 2; ++s2) kl.accumulate(sQ, sO, s2, p[2 * s2], p[2 * s2 + 1], ds[2 * s2], ds[2 * s2 + 1], lane);
     __syncthreads();  // dS^T of every wave in LDS
     // dQ^T[d][q] for the tile's queries 16*wave .. +15 over the workgroup's 128 keys: lane holds d = 16t + 4(lane>>4)
     // .. +3 of query 16*wave + (lane & 15)
@@ -754,25 +732,13 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_fused_kernel(AttnArgs a) {
     }
     const int myq = q0 + wave * 16 + (lane & 15);
     if (nkb == 1) {
-      if (myq < a.N) {
-        bf16_t* DQ = a.dq + ((long long)b * a.N + myq) * a.lddq + h * a.d;
-#pragma unroll
-        for (int t = 0; t < DT; ++t) {
-          const int d0 = 16 * t + (lane >> 4) * 4;
-          if (d0 < a.d) store4(DQ + d0, dq[t], a.scale);
-        }
-      }
+      if (myq < a.N) store_row<DT>(a.dq + ((long long)w.b * a.N + myq) * a.lddq + w.h * a.d, dq, a.d, a.scale, lane);
     } else {
-      if (myq < a.N) {
-#pragma unroll
-        for (int t = 0; t < DT; ++t) {
-          const int d0 = 16 * t + (lane >> 4) * 4;
-          if (d0 < a.d) {
-            const int off = ((((kb * a.B * a.H + bh) * a.N) + myq) * a.d + d0) * 4;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, dq[t]), rsP, off, 0, ATTN_CPOL_SC1);
-          }
-        }
-      }
+      if (myq < a.N)
+        row_chunks<DT>(a.d, lane, [&](int t, int d0) __attribute__((always_inline)) {
+          const int off = ((((w.blk * a.B * a.H + bh) * a.N) + myq) * a.d + d0) * 4;
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, dq[t]), rsP, off, 0, ATTN_CPOL_SC1);
+        });
       // arrival: the partial stores (and the next tile's loads) complete, then one relaxed device-scope increment;
       // the last key block of this (b*h, query tile) sums the partials
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -796,28 +762,12 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_fused_kernel(AttnArgs a) {
             const int off = ((((z * a.B * a.H + bh) * a.N) + q) * a.d + d0) * 4;
             acc += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsP, off, 0, ATTN_CPOL_SC1));
           }
-          store4(a.dq + ((long long)b * a.N + q) * a.lddq + h * a.d + d0, acc, a.scale);
+          store4(a.dq + ((long long)w.b * a.N + q) * a.lddq + w.h * a.d + d0, acc, a.scale);
         }
       }
     }
-    if (more) put(cur ^ 1);
-    __syncthreads();
-    cur ^= 1;
-  }
-#pragma unroll
-  for (int g = 0; g < 2; ++g)
-    if (kok[g]) {
-      bf16_t* DK = a.dk + ((long long)b * a.S + mykey[g]) * a.lddk + h * a.d;
-      bf16_t* DV = a.dv + ((long long)b * a.S + mykey[g]) * a.lddv + h * a.d;
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        int d0 = 16 * t + (lane >> 4) * 4;
-        if (d0 < a.d) {
-          store4(DK + d0, dk[g][t], a.scale);
-          store4(DV + d0, dv[g][t], 1.f);
-        }
-      }
-    }
+  });
+  kl.store(a, w);
 }
 
 // delta[b*h][q] = rowsum(dO * O) over the head's d columns (fp32), one thread per (b, q, h)
@@ -831,13 +781,7 @@ __global__ __launch_bounds__(NT) void attn_delta_kernel(AttnArgs a) {
   const bf16_t* o = a.o + bq * a.ldo + h * a.d;
   const bf16_t* g = a.dout + bq * a.lddo + h * a.d;
   float D = 0.f;
-  for (int c0 = 0; c0 < a.d; c0 += 8) {
-    float x[8], y[8];
-    unpack8(*(const uint4*)(o + c0), x);
-    unpack8(*(const uint4*)(g + c0), y);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) D = fmaf(x[e], y[e], D);
-  }
+  for (int c0 = 0; c0 < a.d; c0 += 8) D = dot8(*(const uint4*)(o + c0), *(const uint4*)(g + c0), D);
   ((float*)a.delta)[((long long)b * a.H + h) * a.N + q] = D;
 }
 
@@ -858,31 +802,54 @@ int check_args(const AttnArgs& a) {
   return 0;
 }
 
+// Fills and checks the kernels' arguments for all three entry points (returns check_args' code). ldo is the row stride
+// of out in the forward, which takes out, lse and none of o .. dv, and of o in the backward, which has no out.
+int make_args(AttnArgs& a, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out,
+              const void* o, int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq,
+              void* dk, int lddk, void* dv, int lddv, int B, int H, int N, int S, int d) {
+  a = {};
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o;
+  a.dout = (const bf16_t*)dout; a.out = (bf16_t*)out; a.lse = (float*)lse; a.delta = delta;
+  a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+  a.B = B; a.H = H; a.N = N; a.S = S; a.d = d; a.scale = 1.0f / sqrtf((float)d);
+  return check_args(a);
+}
+
+// f(std::integral_constant<int, DT>) for DT = ceil(d / 16), the kernels' compile-time count of output column tiles
+template <class F>
+void dispatch_dt(int d, F f) {
+  switch ((d + 15) / 16) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+
+// the 1-D grid of a launch whose workgroups own `rows` rows of `len`: ceil(len / rows) row blocks (a.nblk) per (b, h)
+dim3 grid_for(AttnArgs& a, int len, int rows) {
+  a.nblk = (len + rows - 1) / rows;
+  return dim3(a.nblk * a.B * a.H);
+}
+
 }  // namespace
 
 extern "C" int sdmi_attn_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
                              float* lse, int B, int H, int N, int S, int d, sdmi_stream_t stream) {
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)out; a.lse = lse;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-  a.B = B; a.H = H; a.N = N; a.S = S; a.d = d; a.scale = 1.0f / sqrtf((float)d);
-  int rc = check_args(a);
+  AttnArgs a;
+  int rc = make_args(a, q, ldq, k, ldk, v, ldv, out, nullptr, ldo, nullptr, 0, lse, nullptr, nullptr, 0, nullptr, 0,
+                     nullptr, 0, B, H, N, S, d);
   if (rc) return rc;
-  a.nblk = (N + ROWS - 1) / ROWS;
-  dim3 grid(a.nblk * B * H);
+  const dim3 grid = grid_for(a, N, ROWS);
   hipStream_t s = (hipStream_t)stream;
   // ONES: the softmax row sum through the PV MFMA where the padded head dim leaves a free column (d % 16 == 8)
   const bool ones = d % 16 == 8;
-#define SDMI_ATTN_FWD(DT)                                                           \
-  if (ones) sdmi_rt::launch(attn_fwd_kernel<DT, true>, grid, dim3(NT), 0, s, a);    \
-  else sdmi_rt::launch(attn_fwd_kernel<DT, false>, grid, dim3(NT), 0, s, a);
-  switch ((d + 15) / 16) {
-    case 1: SDMI_ATTN_FWD(1) break;
-    case 2: SDMI_ATTN_FWD(2) break;
-    case 3: SDMI_ATTN_FWD(3) break;
-    default: SDMI_ATTN_FWD(4) break;
-  }
-#undef SDMI_ATTN_FWD
+  dispatch_dt(d, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (ones) sdmi_rt::launch(attn_fwd_kernel<DT, true>, grid, dim3(NT), 0, s, a);
+    else sdmi_rt::launch(attn_fwd_kernel<DT, false>, grid, dim3(NT), 0, s, a);
+  });
   SDMI_CHECK_LAUNCH();
   return 0;
 }
@@ -891,13 +858,9 @@ extern "C" int sdmi_attn_bwd(const void* q, int ldq, const void* k, int ldk, con
                              int ldo, const void* dout, int lddo, const float* lse, float* delta_ws, void* dq, int lddq,
                              void* dk, int lddk, void* dv, int lddv, int B, int H, int N, int S, int d,
                              sdmi_stream_t stream) {
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o;
-  a.dout = (const bf16_t*)dout; a.lse = (float*)lse; a.delta = delta_ws;
-  a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-  a.B = B; a.H = H; a.N = N; a.S = S; a.d = d; a.scale = 1.0f / sqrtf((float)d);
-  int rc = check_args(a);
+  AttnArgs a;
+  int rc = make_args(a, q, ldq, k, ldk, v, ldv, nullptr, o, ldo, dout, lddo, lse, delta_ws, dq, lddq, dk, lddk, dv, lddv,
+                     B, H, N, S, d);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   // the dQ kernel also produces delta = rowsum(dO * O) (written to delta_ws) for the dK/dV kernel after it.
@@ -910,28 +873,19 @@ extern "C" int sdmi_attn_bwd(const void* q, int ldq, const void* k, int ldk, con
   const int g4 = d <= 32 && N <= 256 && S <= 256 && wg4 >= 512;
   const int rows = g4 ? 256 : ROWS;
   AttnArgs aq = a, ak = a;
-  aq.nblk = (N + rows - 1) / rows;
-  ak.nblk = (S + rows - 1) / rows;
-  dim3 gk(ak.nblk * B * H), gq(aq.nblk * B * H);
-  switch ((d + 15) / 16) {
-#define SDMI_ATTN_BWD(DT)                                                               \
-  case DT:                                                                              \
-    if constexpr (DT <= 2) {                                                            \
-      if (g4) {                                                                         \
-        sdmi_rt::launch(attn_bwd_dq_kernel<DT, 4>, gq, dim3(NT), 0, s, aq);             \
-        sdmi_rt::launch(attn_bwd_dkv_kernel<DT, 4>, gk, dim3(NT), 0, s, ak);            \
-        break;                                                                          \
-      }                                                                                 \
-    }                                                                                   \
-    sdmi_rt::launch(attn_bwd_dq_kernel<DT, 2>, gq, dim3(NT), 0, s, aq);                 \
-    sdmi_rt::launch(attn_bwd_dkv_kernel<DT, 2>, gk, dim3(NT), 0, s, ak);                \
-    break;
-    SDMI_ATTN_BWD(1)
-    SDMI_ATTN_BWD(2)
-    SDMI_ATTN_BWD(3)
-    default: SDMI_ATTN_BWD(4)
-#undef SDMI_ATTN_BWD
-  }
+  const dim3 gq = grid_for(aq, N, rows), gk = grid_for(ak, S, rows);
+  dispatch_dt(d, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if constexpr (DT <= 2) {
+      if (g4) {
+        sdmi_rt::launch(attn_bwd_dq_kernel<DT, 4>, gq, dim3(NT), 0, s, aq);
+        sdmi_rt::launch(attn_bwd_dkv_kernel<DT, 4>, gk, dim3(NT), 0, s, ak);
+        return;
+      }
+    }
+    sdmi_rt::launch(attn_bwd_dq_kernel<DT, 2>, gq, dim3(NT), 0, s, aq);
+    sdmi_rt::launch(attn_bwd_dkv_kernel<DT, 2>, gk, dim3(NT), 0, s, ak);
+  });
   SDMI_CHECK_LAUNCH();
   return 0;
 }
@@ -947,13 +901,9 @@ extern "C" int sdmi_attn_bwd_fused(const void* q, int ldq, const void* k, int ld
                                    float* delta_ws, void* ws, size_t ws_bytes, void* dq, int lddq, void* dk,
                                    int lddk, void* dv, int lddv, int B, int H, int N, int S, int d,
                                    sdmi_stream_t stream) {
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o;
-  a.dout = (const bf16_t*)dout; a.lse = (float*)lse; a.delta = delta_ws;
-  a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-  a.B = B; a.H = H; a.N = N; a.S = S; a.d = d; a.scale = 1.0f / sqrtf((float)d);
-  int rc = check_args(a);
+  AttnArgs a;
+  int rc = make_args(a, q, ldq, k, ldk, v, ldv, nullptr, o, ldo, dout, lddo, lse, delta_ws, dq, lddq, dk, lddk, dv, lddv,
+                     B, H, N, S, d);
   if (rc) return rc;
   const size_t need = sdmi_attn_bwd_workspace(B, H, N, S, d);
   const long long ntq = (N + TILE - 1) / TILE;
@@ -973,14 +923,9 @@ extern "C" int sdmi_attn_bwd_fused(const void* q, int ldq, const void* k, int ld
   hipStream_t s = (hipStream_t)stream;
   const long long rows = (long long)B * N * H;
   sdmi_rt::launch(attn_delta_kernel, dim3((unsigned)((rows + NT - 1) / NT)), dim3(NT), 0, s, a);
-  a.nblk = (S + ROWS - 1) / ROWS;
-  dim3 gk(a.nblk * B * H);
-  switch ((d + 15) / 16) {
-    case 1: sdmi_rt::launch(attn_bwd_fused_kernel<1>, gk, dim3(NT), 0, s, a); break;
-    case 2: sdmi_rt::launch(attn_bwd_fused_kernel<2>, gk, dim3(NT), 0, s, a); break;
-    case 3: sdmi_rt::launch(attn_bwd_fused_kernel<3>, gk, dim3(NT), 0, s, a); break;
-    default: sdmi_rt::launch(attn_bwd_fused_kernel<4>, gk, dim3(NT), 0, s, a); break;
-  }
+  const dim3 gk = grid_for(a, S, ROWS);
+  dispatch_dt(d, [&](auto dt) { sdmi_rt::launch(attn_bwd_fused_kernel<decltype(dt)::value>, gk, dim3(NT), 0, s, a); });
   SDMI_CHECK_LAUNCH();
   return 0;
 }
+
