@@ -304,7 +304,9 @@ int sdmi_mse_patch(const float* pred, int ld, const float* target, int B, int C,
  *                     - 2 x.e, 0)) with first-minimum argmin, straight-through output zq = x + (q - x) (NCHW fp32),
  *                     int64 indices (B*H*W), optional pre-quantisation latent xq (NCHW fp32) and the codebook /
  *                     commitment loss mean((q - x)^2). ws: sdmi_vq_workspace(B*HW) bytes.
- *  sdmi_pointwise_in: post_quant_conv (1x1, fp32) of an NCHW fp32 latent into NHWC bf16 [P][ld] (tail zeroed).
+ *  sdmi_pointwise_in: post_quant_conv (1x1, fp32) of an NCHW fp32 latent into NHWC bf16 [P][ld] (tail zeroed). w
+ *                     (cout, C) is required (NULL returns -1: the identity form exists only in sdmi_vq_quantize);
+ *                     b (cout) may be NULL.
  * ------------------------------------------------------------------------------------------- */
 /*  sdmi_vq_bwd      : training backward of the latent interface (train_vqvae_celebhq.py:405-430, recon + codebook
  *                     + commitment terms; LPIPS enters through the reconstruction gradient, see the LPIPS section; the

@@ -431,7 +431,7 @@ extern "C" int sdmi_vq_quantize(const float* z, int ldz, const float* w, const f
 
 extern "C" int sdmi_pointwise_in(const float* z, int B, int C, int HW, const float* w, const float* b, int cout,
                                  void* out, int ld, sdmi_stream_t stream) {
-  if (!z || !out || B <= 0 || C <= 0 || HW <= 0 || cout <= 0 || ld < cout) return -1;
+  if (!z || !w || !out || B <= 0 || C <= 0 || HW <= 0 || cout <= 0 || ld < cout) return -1;
   const long long total = (long long)B * HW * ld;
   const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
   sdmi_rt::launch(pointwise_in_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, B, C, HW, w, b, cout,
