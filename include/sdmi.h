@@ -482,8 +482,16 @@ int sdmi_loss_flag(const float* src, float* dst, int mode, sdmi_stream_t stream)
  * skip / scaler update above. */
 int sdmi_clip_finalize(const float* partial, int n, float max_norm, float* state, int growth_interval,
                        int skip_if_loss_nonfinite, float grad_div, sdmi_stream_t stream);
-/* ema_alpha: the fp32 value of (1 - ema_decay) as the caller computes it (the reference passes alpha = 1 - 0.9999
- * from Python doubles, :376-378) */
+/* Adam as this ABI defines it (tests/optim_matrix.py pins it): b1 and b2 are the floats passed; the complements are
+ * the exact fp32 differences 1.f - b1 and 1.f - b2 (exact by Sterbenz for b in [0.5, 1]); the bias corrections are
+ * 1 - (double)b ^ step in double, step = (int)state[4], with step_size = (float)(lr / bc1) and (float)sqrt(bc2) rounded
+ * once; the gradient is grads[i] * state[1]. torch.optim.Adam fed the Python doubles 0.9 / 0.999 multiplies by
+ * float(1 - 0.9) and float(1 - 0.999) instead: 1.f - 0.999f = 0.0009999871 against 0.001 is a systematic relative
+ * difference of 1.29e-5 on every element of v (2.2e-7 on m for 0.9), not rounding noise.
+ * params, grads, m, v, state null or n < 0: -1; n == 0: 0, nothing launched; ema null: no EMA. 16-byte aligned
+ * operands (and an 8-byte aligned params_bf16) take the 4-wide kernel, anything else the scalar one.
+ * ema_alpha: the fp32 value of (1 - ema_decay) as the caller computes it (the reference passes alpha = 1 - 0.9999
+ * from Python doubles, :376-378); ema = fma(ema_alpha, p, fl(ema * ema_decay)). */
 int sdmi_adam_ema(float* params, const float* grads, float* m, float* v, float* ema, long long n, const float* state,
                   float lr, float b1, float b2, float eps, float ema_decay, float ema_alpha, sdmi_stream_t stream);
 /* The same step also writing params_bf16[i] = bf16(params[i]) (round to nearest even; untouched on a skipped step):

@@ -308,6 +308,8 @@ extern "C" int sdmi_cast_bf16(const float* src, void* dst, long long n, sdmi_str
 extern "C" int sdmi_adam_ema_bf16(float* params, const float* grads, float* m, float* v, float* ema, long long n,
                                   const float* state, float lr, float b1, float b2, float eps, float ema_decay,
                                   float ema_alpha, void* params_bf16, sdmi_stream_t stream) {
+  if (!params || !grads || !m || !v || !state || n < 0) return -1;  // (ema and params_bf16 are optional)
+  if (n == 0) return 0;
   const bool vec = ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0) &&
                    ((uintptr_t)params_bf16 & 7) == 0;
   long long blocks = (n / (vec ? 4 : 1) + NT - 1) / NT;

@@ -84,8 +84,11 @@ def test_state_machine_matches_torch_gradscaler_adam():
         assert torch.allclose(ema, ema_t, rtol=2e-6, atol=1e-7), (i, ev)
         if p_t in opt.state:
             assert torch.allclose(m, opt.state[p_t]["exp_avg"], rtol=1e-5, atol=1e-9), (i, ev)
-            # v = g^2 doubles the clip coefficient's relative difference
-            assert torch.allclose(v, opt.state[p_t]["exp_avg_sq"], rtol=4e-5, atol=1e-12), (i, ev)
+            # a definitional difference, not rounding: the kernel multiplies g^2 by the exact fp32 complement
+            # 1.f - 0.999f = 0.0009999871, torch by float(1 - 0.999) = 0.001, so every element of v sits 1.29e-5 below
+            # torch's at every step (tests/optim_matrix.py complement_gap; test_optim_exact_gpu.py measures the GPU's v
+            # against both models). The clip coefficient's few ulp, squared, and the roundings of v add about 1e-6.
+            assert torch.allclose(v, opt.state[p_t]["exp_avg_sq"], rtol=2e-5, atol=1e-12), (i, ev)
     # the sequence grew the scale three times and backed it off twice: 65536 * 2 / 2 * 2 * 2 / 2
     assert scaler.get_scale() == 131072.0 and state[S_SCALE].item() == 131072.0
 
