@@ -234,7 +234,8 @@ int sdmi_chan_sum(const void* dy, int lddy, int B, int P, int C, float* ws, void
  *  sdmi_prep_input_cmap / sdmi_cond_wgrad_cmap : the same with the mask given as a uint8 class map
  *                      (B,MH,MW) instead of the (B,cmi,MH,MW) fp32 one-hot that dataset/celeb_dataset.py:164-175
  *                      builds (clamp(0,cmi) -> one_hot(cmi+1) -> drop background); bit-identical results.
- *  sdmi_add_noise    : scheduler/linear_noise_scheduler.py:26-48 (bit-exact fp32 mul/mul/add).
+ *  sdmi_add_noise    : scheduler/linear_noise_scheduler.py:26-48 (bit-exact fp32 mul/mul/add). Returns -1 on a NULL
+ *                      pointer or B <= 0 or per_sample <= 0, before any launch.
  *  sdmi_mse          : nn.MSELoss (train_ddpm_cond_celebhq_multi_gpu.py:267,346) + its gradient times
  *                      the loss scale (gscale or *gscale_dev, GradScaler :269,362).
  *  sdmi_time_embedding: models/blocks.py:5-24 (t stride 0 broadcasts one timestep).
@@ -372,8 +373,10 @@ int sdmi_lpips_mean(const float* val, int B, float scale, float* out, sdmi_strea
  * Sampling steps (scheduler/linear_noise_scheduler.py), fp32 elementwise, bit-exact to the reference given the
  * same noise (correctly rounded fp32 div / sqrt, no FMA contraction).
  *  sdmi_ddpm_prev : LinearNoiseScheduler.sample_prev_timestep (:50-78); timestep read from device memory
- *                   (t_dev), z unused at t == 0, x0 (clamped prediction) optional; decrement_t: t_dev -= 1 after
- *                   the step (capturable sampling loop, no host round trip per step).
+ *                   (t_dev), z unused at t == 0 and NULL meaning zero noise at any t (mean + sigma * 0, as in
+ *                   sdmi_ddim_prev and sdmi_affine_step), x0 (clamped prediction) optional, clamped as torch.clamp
+ *                   does: a NaN prediction stays NaN; decrement_t: t_dev -= 1 after the step (capturable sampling
+ *                   loop, no host round trip per step).
  *  sdmi_ddim_prev : DDIMSampler.sample_one_step (:164-182) for alpha_t = abar[t], alpha_prev = abar[t_prev].
  *  sdmi_ddim_prev_dev: the same DDIM step with the pair read on the device: i = *idx, alpha_t = abar[ts[i]],
  *                   alpha_prev = abar[tp[i]] (DDIMSampler.forward's time_steps / time_steps_prev, :231-242); advance:

@@ -472,6 +472,7 @@ extern "C" int sdmi_nchw_to_nhwc_bf16(const float* src, int B, int C, int HW, vo
 extern "C" int sdmi_add_noise(const float* x0, const float* eps, const long long* t, const float* sqrt_abar,
                               const float* sqrt_one_minus_abar, int B, long long per_sample, float* out,
                               sdmi_stream_t stream) {
+  if (!x0 || !eps || !t || !sqrt_abar || !sqrt_one_minus_abar || !out || B <= 0 || per_sample <= 0) return -1;
   sdmi_rt::launch(add_noise_kernel, dim3(grid_for((long long)B * per_sample)), dim3(NT), 0, (hipStream_t)stream, x0,
                      eps, t, sqrt_abar, sqrt_one_minus_abar, B, per_sample, out);
   SDMI_CHECK_LAUNCH();

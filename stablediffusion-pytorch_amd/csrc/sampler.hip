@@ -47,11 +47,11 @@ __global__ void ddpm_prev_kernel(const float* xt, const float* eps, const float*
   for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
     const float x = xt[i], e = eps[i];
     float x0 = div_ieee(sub_ieee(x, mul_ieee(s1, e)), sq_abar);
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    x0 = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);  // torch.clamp: a NaN prediction stays NaN (fminf / fmaxf drop it)
     float mean = sub_ieee(x, div_ieee(mul_ieee(beta, e), s1));
     mean = div_ieee(mean, sq_alpha);
     if (x0out) x0out[i] = x0;
-    const float p = t > 0 ? add_ieee(mean, mul_ieee(sigma, z[i])) : mean;
+    const float p = t > 0 ? add_ieee(mean, mul_ieee(sigma, z ? z[i] : 0.0f)) : mean;  // z NULL: zero noise
     prev[i] = p;
     if (prev2) prev2[i] = p;
   }
