@@ -332,6 +332,38 @@ int sdmi_pointwise_in(const float* z, int B, int C, int HW, const float* w, cons
                       int ld, sdmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Latent-range noise of the noise-robust VQVAE (models/vqvae_noise.py:155,177-183):
+ *     out = z + (z.max() - z.min()) * n_scale * eps        between quantize() and decode().
+ * All tensors are contiguous fp32 NCHW latents of n = B*C*HW < 2^31 elements, C <= 8 (a flat tensor is B = C = 1).
+ * No atomics, every sum in a fixed order: a second call repeats every bit. n_scale is an fp32 launch argument.
+ *  sdmi_latent_noise_workspace(n): bytes of either workspace below (16 per range workgroup, min(256, ceil(n / 1024))).
+ *  sdmi_latent_range   : per-workgroup partials {min, max, cnt_min, cnt_max (int bits)} of z into ws; the counts are
+ *                        the elements equal to each extreme, -0.0 == +0.0, a NaN anywhere makes both extremes NaN.
+ *                        The consumers below merge the partials themselves (no finaliser launch).
+ *  sdmi_latent_noise_fwd: out[i] = fl(z[i] + fl(fl(fl(max - min) * n_scale) * eps[i])), nothing contracted (the
+ *                        torch expression's rounding order). zin != NULL: the same launch also writes
+ *                        post_quant_conv(out) as NHWC bf16 [P][ld] with the arithmetic of sdmi_pointwise_in (fma
+ *                        chain from the bias, ci ascending, RNE, pad columns zero; cout <= 8); it then replaces that
+ *                        launch. zin without w_post returns -1. ws: the partials sdmi_latent_range wrote for z.
+ *  sdmi_latent_noise_bwd: g = W_post^T dzin (fma chain, co ascending) + dz_add -- the dzq arithmetic of sdmi_vq_bwd --
+ *                        S = sum g * eps (two stages, fixed order; partials in ws), c_max = fl(fl(n_scale S) /
+ *                        cnt_max), c_min likewise, r[i] = fl(dz_add[i] + corr[i]) with corr = c_max where z[i] == max,
+ *                        -c_min where z[i] == min, fl(c_max - c_min) where both, else 0. z is the CLEAN latent the
+ *                        range was taken of. dzin (NHWC bf16 [P][ld_dzin]) or dz_add may be NULL, not both. r is the
+ *                        dzq_add of sdmi_vq_bwd, whose zq argument is then the noisy latent (post_quant_conv's input).
+ * n_scale == 0: fwd and bwd launch nothing, read no eps and return 0 (the caller keeps z / dz_add).
+ * Launches: range 1, fwd 1, bwd 2.
+ * ------------------------------------------------------------------------------------------- */
+size_t sdmi_latent_noise_workspace(long long n);
+int sdmi_latent_range(const float* z, long long n, float* ws, sdmi_stream_t stream);
+int sdmi_latent_noise_fwd(const float* z, const float* eps, int B, int C, int HW, float n_scale, const float* ws,
+                          float* out, const float* w_post, const float* b_post, int cout, void* zin, int ld,
+                          sdmi_stream_t stream);
+int sdmi_latent_noise_bwd(const void* dzin, int ld_dzin, const float* w_post, const float* dz_add, const float* eps,
+                          const float* z, int B, int C, int HW, float n_scale, const float* ws_range, float* ws,
+                          float* r, sdmi_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * LPIPS perceptual loss (models/lpips.py) around the VGG16 convolutions (sdmi_gemm, act 2 / 3). NHWC bf16
  * activations, fp32 arithmetic, fixed-order reductions (bitwise repeatable, no atomics).
  *  sdmi_lpips_prep       : ScalingLayer + packing. out [2B*H*W][8] bf16 = (x - shift[c]) / scale[c] of in0 (rows

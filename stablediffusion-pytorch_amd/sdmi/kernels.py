@@ -636,3 +636,30 @@ def lpips_dist_bwd(f, w, rn, B, P, C, side, dy, *, g=None, gscale=1.0, addend=No
 
 def lpips_mean(val, B, scale, out):
     check(_lib.lib().sdmi_lpips_mean(_p(val), B, float(scale), _p(out), _stream()), "sdmi_lpips_mean")
+
+
+# ---- latent-range noise of the noise-robust VQVAE (csrc/latent_noise.hip; models/vqvae_noise.py:177-183) ----
+def latent_noise_ws(n, device):
+    """One workspace of sdmi_latent_noise_workspace(n) bytes (the range partials, or the backward's S partials)."""
+    return torch.empty(max(_lib.lib().sdmi_latent_noise_workspace(n) // 4, 1), dtype=torch.float32, device=device)
+
+
+def latent_range(z, ws):
+    check(_lib.lib().sdmi_latent_range(_p(z), z.numel(), _p(ws), _stream()), "sdmi_latent_range")
+    return ws
+
+
+def latent_noise_fwd(z, eps, B, C, HW, n_scale, ws, out, *, w_post=None, b_post=None, cout=0, zin=None, ld=0):
+    """out = z + (max - min) n_scale eps on the range partials `ws` of z; with zin also post_quant_conv(out) as the
+    NHWC bf16 operand of decoder_conv_in (replaces the sdmi_pointwise_in launch)."""
+    check(_lib.lib().sdmi_latent_noise_fwd(_p(z), _p(eps), B, C, HW, float(n_scale), _p(ws), _p(out), _p(w_post),
+                                           _p(b_post), cout, _p(zin), ld, _stream()), "sdmi_latent_noise_fwd")
+    return out
+
+
+def latent_noise_bwd(dzin, ld_dzin, w_post, dz_add, eps, z, B, C, HW, n_scale, ws_range, ws, r):
+    """r = dz_add + the range gradient of the noise (the dzq_add of sdmi_vq_bwd); z is the clean latent."""
+    check(_lib.lib().sdmi_latent_noise_bwd(_p(dzin), ld_dzin, _p(w_post), _p(dz_add), _p(eps), _p(z), B, C, HW,
+                                           float(n_scale), _p(ws_range), _p(ws), _p(r), _stream()),
+          "sdmi_latent_noise_bwd")
+    return r

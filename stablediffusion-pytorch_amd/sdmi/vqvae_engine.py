@@ -175,9 +175,11 @@ class VQVAEEngine:
         return out
 
     # ------------------------------------------------------------------------------------------
-    def encode(self, x, want_pre_quant=False):
+    def encode(self, x, want_pre_quant=False, n_scale=0.0, eps=None):
         """vqvae.py:128-139. x: (B, 3, H, W) fp32 -> (z_q NCHW fp32, loss (1,), indices int64 (B, h, w)
-        [, pre-quantisation latent NCHW fp32])."""
+        [, pre-quantisation latent NCHW fp32]). n_scale != 0 (vqvae_noise.py:155): the returned z_q is z_q +
+        (max - min) n_scale eps, eps (z_q's shape, fp32) the caller's standard-normal draw; the loss and the indices
+        are the clean latent's."""
         L, P = self.L, self.P
         B, Cx, H, W = x.shape
         assert Cx == self.im_channels
@@ -216,6 +218,12 @@ class VQVAEEngine:
                                                P["pre_quant_conv.bias"].data_ptr(), P["embedding.weight"].data_ptr(),
                                                L["K"], B, h * w, L["z"], zq.data_ptr(), idx.data_ptr(), K._p(pre),
                                                ws.data_ptr(), loss.data_ptr(), K._stream()), "sdmi_vq_quantize")
+        if float(n_scale) != 0.0:
+            if eps is None:
+                raise ValueError("n_scale != 0 needs eps, the standard-normal draw of the latent's shape")
+            clean, zq = zq, torch.empty_like(zq)
+            rws = K.latent_range(clean, K.latent_noise_ws(clean.numel(), self.device))
+            K.latent_noise_fwd(clean, plan.as_operand(eps), B, L["z"], h * w, n_scale, rws, zq)
         if want_pre_quant:
             return zq, loss, idx, pre
         return zq, loss, idx

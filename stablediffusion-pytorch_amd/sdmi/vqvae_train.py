@@ -113,10 +113,16 @@ class VQVAETrainEngine(UNetEngine):
         self.pack = pk
 
     # ------------------------------------------------------------------------------------------
-    def forward(self, x, need_backward=True):
+    def latent_shape(self, B, H, W):
+        f = 2 ** sum(1 for d in self.L["ds"] if d)
+        return (B, self.L["z"], H // f, W // f)
+
+    def forward(self, x, need_backward=True, n_scale=0.0, eps=None):
         """x: (B, im_channels, H, W) fp32 image. Returns (reconstruction NHWC fp32 [B*H*W, 8] with the first
         im_channels valid, ctx); ctx["vq_loss"] (1,) = mean((q - x)^2) (the codebook and the commitment loss share
-        this value), ctx["indices"] (B, h, w) int64."""
+        this value), ctx["indices"] (B, h, w) int64. n_scale != 0 (vqvae_noise.py:155): the decoder sees zq + (max -
+        min) n_scale eps, eps a standard-normal fp32 tensor of latent_shape(B, H, W); ctx["z"] is that noisy latent,
+        ctx["eps"] and ctx["range_ws"] what the backward reads again, ctx["zq"] stays the clean latent."""
         L, P = self.L, self.P
         B, Cx, H, W = x.shape
         assert Cx == self.im_channels
@@ -182,9 +188,22 @@ class VQVAETrainEngine(UNetEngine):
         # ---- decoder (vqvae.py:141-153) ----
         tape.label = "decoder_in"
         zin = self._new(B * Pn, 8)
-        _lib.check(_lib.lib().sdmi_pointwise_in(zq.data_ptr(), B, zc, Pn, P["post_quant_conv.weight"].data_ptr(),
-                                                P["post_quant_conv.bias"].data_ptr(), zc, zin.data_ptr(), 8,
-                                                K._stream()), "sdmi_pointwise_in")
+        noise = {}
+        if float(n_scale) != 0.0:  # range + one launch that adds the noise and applies post_quant_conv
+            if eps is None or tuple(eps.shape) != tuple(zq.shape):
+                raise ValueError("n_scale != 0 needs eps, a standard-normal draw of latent_shape(B, H, W)")
+            eps = plan.as_operand(eps)
+            zn = torch.empty_like(zq)
+            rws = K.latent_range(zq, K.latent_noise_ws(zq.numel(), self.device))
+            K.latent_noise_fwd(zq, eps, B, zc, Pn, n_scale, rws, zn, w_post=P["post_quant_conv.weight"],
+                               b_post=P["post_quant_conv.bias"], cout=zc, zin=zin, ld=8)
+            noise = dict(z=zn, eps=eps, range_ws=rws)
+            # (q["z"] is encoder_conv_out's output, the z_enc of sdmi_vq_bwd: the noisy latent goes by another name)
+            q.update(noisy=zn, eps=eps, range_ws=rws, n_scale=float(n_scale))
+        else:
+            _lib.check(_lib.lib().sdmi_pointwise_in(zq.data_ptr(), B, zc, Pn, P["post_quant_conv.weight"].data_ptr(),
+                                                    P["post_quant_conv.bias"].data_ptr(), zc, zin.data_ptr(), 8,
+                                                    K._stream()), "sdmi_pointwise_in")
         cur, name = self._new(B * Pn, m[-1]), "dec_in"
         K.conv_fwd(zin, B, h, w, 8, 8, self.W("decoder_conv_in#f"), m[-1], 3, 3, 1, 1, cur, m[-1],
                    bias=P["decoder_conv_in.bias"])
@@ -216,7 +235,7 @@ class VQVAETrainEngine(UNetEngine):
         K.conv_fwd(hs, B, h, w, d[0], d[0], self.W("decoder_conv_out#f"), 8, 3, 3, 1, 1, out, 8,
                    bias=P["decoder_conv_out.bias"], n_store=self.im_channels)
         tape.append((self._bwd_dec_out, dict(x=cur, xn=name, tab=tab, hs=hs, B=B, H=h, W=w)))
-        ctx = dict(tape=tape, st=st, grads=grads, vq_loss=vq_loss, indices=idx, zq=zq, pre_quant=pre)
+        ctx = dict(tape=tape, st=st, grads=grads, vq_loss=vq_loss, indices=idx, zq=zq, pre_quant=pre, **noise)
         if not need_backward:
             ctx.pop("tape")
         return out, ctx
@@ -262,19 +281,27 @@ class VQVAETrainEngine(UNetEngine):
 
     def _bwd_quant(self, c, grads):
         """sdmi_vq_bwd: post_quant_conv dW/db, straight-through + commitment gradient, pre_quant_conv dW/db, the
-        codebook gradient and the gradient of encoder_conv_out's output (all on the critical path)."""
+        codebook gradient and the gradient of encoder_conv_out's output (all on the critical path). With noise in
+        the forward, sdmi_latent_noise_bwd first turns the outside gradient of the (noisy) latent into dzq_add plus
+        the range gradient at the clean latent's extremes; post_quant_conv's input was the noisy latent."""
         q = c["q"]
         B, h, w = q["B"], q["h"], q["w"]
         L, P = self.L, self.P
+        zq_in, dzq_add = q["zq"], self.dzq_add
+        if "eps" in q:
+            zq_in, dzq_add = q["noisy"], torch.empty_like(q["zq"])
+            K.latent_noise_bwd(q["dzin"], 8, P["post_quant_conv.weight"], self.dzq_add, q["eps"], q["zq"], B, L["z"],
+                               h * w, q["n_scale"], q["range_ws"], K.latent_noise_ws(q["zq"].numel(), self.device),
+                               dzq_add)
         q["dz"] = dz = self._new(B * h * w, 8)
         ws = torch.empty(_lib.lib().sdmi_vq_bwd_workspace() // 4, dtype=torch.float32, device=self.device)
         _lib.check(_lib.lib().sdmi_vq_bwd(
-            q["dzin"].data_ptr(), 8, q["zq"].data_ptr(), P["post_quant_conv.weight"].data_ptr(), q["pre"].data_ptr(),
+            q["dzin"].data_ptr(), 8, zq_in.data_ptr(), P["post_quant_conv.weight"].data_ptr(), q["pre"].data_ptr(),
             q["idx"].data_ptr(), P["embedding.weight"].data_ptr(), L["K"], q["z"].data_ptr(), 8,
             P["pre_quant_conv.weight"].data_ptr(), B, h * w, L["z"], self.commitment_beta, self.codebook_weight,
             dz.data_ptr(), 8, ws.data_ptr(), self.g("post_quant_conv.weight").data_ptr(),
             self.g("post_quant_conv.bias").data_ptr(), self.g("pre_quant_conv.weight").data_ptr(),
-            self.g("pre_quant_conv.bias").data_ptr(), self.g("embedding.weight").data_ptr(), K._p(self.dzq_add),
+            self.g("pre_quant_conv.bias").data_ptr(), self.g("embedding.weight").data_ptr(), K._p(dzq_add),
             K._p(self.loss_w), K._stream()), "sdmi_vq_bwd")
 
     def _bwd_enc_out(self, c, grads):
@@ -329,17 +356,30 @@ class VQVAETrainEngine(UNetEngine):
         K.PHASE = ""
 
 
+def noise_key(noise_seed, rank=0):
+    """The Philox key of a rank's latent noise: ranks must not share noise, so key = noise_seed + rank (mod 2^64)."""
+    return (int(noise_seed) + int(rank)) & 0xFFFFFFFFFFFFFFFF
+
+
 class VQVAETrainer:
     """The generator step of train_vqvae_celebhq.py:405-470 without the GAN term: forward, recon MSE + codebook
     (weight codebook_weight) + commitment (commitment_beta) losses, backward, Adam(lr, betas=(0.5, 0.999)).
     With lpips_state (an LPIPS state dict) and a non-zero perceptual_weight the step adds perceptual_weight *
     mean_b LPIPS(out, im) (train_vqvae_celebhq.py:427-428); by default no LPIPS engine exists and the step is unchanged.
     Flat fp32 parameter / gradient / moment buffers; the step never synchronises with the host. With N > 1 ranks
-    the gradients are averaged over the process group (one bucketed all-reduce after the backward) before Adam."""
+    the gradients are averaged over the process group (one bucketed all-reduce after the backward) before Adam.
+
+    n_scale (settable attribute, default 0): the noise-robust autoencoder of train_vqvae_celebhq_noise_multi_GPU.py --
+    the decoder sees zq + (zq.max() - zq.min()) * n_scale * eps (models/vqvae_noise.py:177-183). eps is drawn on the
+    device by sdmi_randn(key = noise_key(noise_seed, rank), offset), the offset a device counter owned by the trainer
+    that advances with every draw, so every step -- and every replay of a recorded step -- draws fresh, reproducible
+    noise. n_scale is a launch argument: a recorded StepPlan keeps the value it was recorded with and must be recorded
+    again after n_scale changes (the reference's staged schedule changes it a few times per run), as guidance_scale
+    in sdmi.sampling. With n_scale == 0 nothing is allocated or launched for the noise. state_dict() is unchanged."""
 
     def __init__(self, cfg, state_dict, device, *, im_channels=3, lr=2e-5, betas=(0.5, 0.999), eps=1e-8,
                  codebook_weight=1.0, commitment_beta=0.2, group=None, bucket_bytes=64 << 20,
-                 perceptual_weight=0.0, lpips_state=None):
+                 perceptual_weight=0.0, lpips_state=None, n_scale=0.0, noise_seed=0):
         from .reducer import BucketReducer
         self.cfg = cfg
         self.device = torch.device(device)
@@ -365,6 +405,10 @@ class VQVAETrainer:
         self.vq_loss = None
         self.indices = None
         self.lpips = None
+        rank = dist.get_rank(group) if self.world > 1 else 0
+        self.noise_key = noise_key(noise_seed, rank)
+        self.noise_offset = None  # the device draw counter, allocated with the first non-zero n_scale
+        self.n_scale = n_scale
         if perceptual_weight and lpips_state is None:
             raise ValueError("perceptual_weight is set but no LPIPS weights were given (lpips_state=)")
         if perceptual_weight and lpips_state is not None:
@@ -375,12 +419,33 @@ class VQVAETrainer:
             self.lpips = LPIPSEngine(lpips_state, self.device)
             self.lp_loss = torch.zeros(1, dtype=torch.float32, device=self.device)  # the weighted perceptual loss
 
+    @property
+    def n_scale(self):
+        return self._n_scale
+
+    @n_scale.setter
+    def n_scale(self, value):
+        self._n_scale = float(value)
+        if self._n_scale != 0.0 and self.noise_offset is None:
+            self.noise_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def _draw(self, shape):
+        """eps ~ N(0, 1) of the latent's shape at the trainer's (key, device offset); the offset advances."""
+        import ctypes
+        eps = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().sdmi_randn(eps.data_ptr(), eps.numel(), ctypes.c_ulonglong(self.noise_key),
+                                         self.noise_offset.data_ptr(), 1, K._stream()), "sdmi_randn")
+        return eps
+
     def step(self, im):
         """One generator step on a device image batch (B, im_channels, H, W) fp32 in [-1, 1]."""
         eng, st, hp = self.engine, self.store, self.hp
         B, C, H, W = im.shape
         self._shape = (B, C, H, W)
-        out, ctx = eng.forward(im)
+        if self._n_scale != 0.0:
+            out, ctx = eng.forward(im, n_scale=self._n_scale, eps=self._draw(eng.latent_shape(B, H, W)))
+        else:
+            out, ctx = eng.forward(im)
         dout = eng.new_dpred(B, H, W)
         if self.lpips is None:
             K.mse(out, 8, plan.as_operand(im), B, C, H * W, 1.0, dout, self.state[S_LOSS:S_LOSS + 1])
@@ -398,6 +463,7 @@ class VQVAETrainer:
             self.reducer.ready(st.numel)
             self.reducer.finish()
         self.vq_loss, self.indices, self.out = ctx["vq_loss"], ctx["indices"], out
+        self.eps, self.zq, self.z = ctx.get("eps"), ctx["zq"], ctx.get("z", ctx["zq"])
         L = _lib.lib()
         wsb = L.sdmi_optim_workspace_for(st.numel)
         ws = torch.empty(wsb // 4, dtype=torch.float32, device=self.device)
