@@ -239,6 +239,19 @@ int sdmi_chan_sum(const void* dy, int lddy, int B, int P, int C, float* ws, void
  *  sdmi_mse          : nn.MSELoss (train_ddpm_cond_celebhq_multi_gpu.py:267,346) + its gradient times
  *                      the loss scale (gscale or *gscale_dev, GradScaler :269,362).
  *  sdmi_time_embedding: models/blocks.py:5-24 (t stride 0 broadcasts one timestep).
+ * Every entry point of this section returns -1 before any launch for a NULL required pointer or a non-positive size:
+ *  sdmi_prep_input(_cmap): x, out, B, cx, H, W, cpad (a multiple of 8, <= 16, >= cx + cmo); with a mask also wcond,
+ *                      cmi (cmap: 1..255 always, a class is a byte; the fp32 form has no upper limit), MH, MW, cmo.
+ *                      mask / cmap NULL: no mask channels (cmi, cmo, wcond unused). keep is optional.
+ *  sdmi_cond_wgrad(_cmap): dxin, mask / cmap, dw, B, H, W, MH, MW, cmo in 1..16, cmi in 1..255, cx >= 0,
+ *                      ld >= cx + cmo. keep is optional.
+ *  sdmi_nhwc_to_nchw / sdmi_nchw_to_nhwc_bf16: src, dst, B, C, HW, ld >= C.
+ *  sdmi_mse          : pred, target, ws (sdmi_mse_workspace() bytes), loss, B, C, HW, ld >= C. grad and gscale_dev are
+ *                      optional.
+ *  sdmi_time_embedding: t, out, B, dim (even), ld >= dim, tstride >= 0. out_f32 (B, dim) is optional.
+ *  sdmi_silu         : x, y, n > 0; dy optional (present: the backward dx = dy silu'(x)). bf16 in and out, fp32
+ *                      arithmetic; normal results down to x = -88.5, -0 (backward: a zero) for x <= -89, as torch fp32.
+ *  sdmi_copy_slice   : src, dst, P, C, lds >= C, ldd >= C, all three multiples of 8.
  * ------------------------------------------------------------------------------------------- */
 int sdmi_prep_input(const float* x, int B, int cx, int H, int W, const float* mask, int cmi, int MH, int MW,
                     const float* wcond, int cmo, void* out, int cpad, const float* keep, sdmi_stream_t stream);
@@ -259,7 +272,9 @@ int sdmi_mse(const float* pred, int ld, const float* target, int B, int C, int H
 int sdmi_time_embedding(const long long* t, int tstride, int B, int dim, void* out, int ld, float* out_f32,
                         sdmi_stream_t stream);
 int sdmi_silu(const void* x, const void* dy, void* y, long long n, sdmi_stream_t stream);
-/* fp32 ReLU (dy NULL) or its backward dx = dy * (x > 0) (the leaf path's nn.ReLU, transformer.py:72,80) */
+/* fp32 ReLU y = x <= 0 ? +0 : x (dy NULL) or its backward dx = x <= 0 ? 0 : dy (the leaf path's nn.ReLU,
+ * transformer.py:72,80): a NaN x gives NaN forward and passes dy backward, as torch's relu and threshold_backward do.
+ * x or y NULL or n < 0: -1; n == 0: 0, nothing launched. */
 int sdmi_relu(const float* x, const float* dy, float* y, long long n, sdmi_stream_t stream);
 int sdmi_copy_slice(const void* src, int lds, void* dst, int ldd, long long P, int C, int accumulate,
                     sdmi_stream_t stream);

@@ -60,6 +60,24 @@ __device__ __forceinline__ float silu_grad_f(float x) {
   return s * (1.0f + x * (1.0f - s));
 }
 
+// silu_f / silu_grad_f for the stand-alone kernel (sdmi_silu), not the fused epilogues: four more VALU ops per element.
+// v_rcp_f32 flushes a subnormal result, so silu_f returns -0 for x in (-89, -87.3], where 1 + 2^(-x log2 e) exceeds
+// 2^126 but silu(x) is still a normal number (-3.3e-37 at -88.5; torch's fp32 silu returns it). Here the reciprocal is
+// taken of 2^-64 times the sum where the sum exceeds 2^64 (x < -44.4) and the product is scaled back; wherever the
+// scale is 1 the operations are those of silu_f / silu_grad_f. x <= -89 (the sum overflows) still gives -0, as in torch.
+__device__ __forceinline__ float silu_wide_f(float x) {
+  const float d = 1.0f + fast_exp2(-x * kLog2e);
+  const float sc = d > 0x1p64f ? 0x1p-64f : 1.0f;
+  return (x * fast_rcp(d * sc)) * sc;
+}
+
+__device__ __forceinline__ float silu_grad_wide_f(float x) {
+  const float d = 1.0f + fast_exp2(-x * kLog2e);
+  const float sc = d > 0x1p64f ? 0x1p-64f : 1.0f;
+  const float r = fast_rcp(d * sc);  // s / sc
+  return (r * (1.0f + x * (1.0f - r * sc))) * sc;
+}
+
 __device__ __forceinline__ void unpack8(const uint4& v, float* f) {
   f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
   f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);

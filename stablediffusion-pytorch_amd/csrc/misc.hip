@@ -119,6 +119,7 @@ int cw_slot() {
 template <bool CMAP>
 int launch_cond_wgrad(const void* dxin, int ld, int cx, int B, int H, int W, const void* mask, int cmi, int MH, int MW,
                       int cmo, float* dw, const float* keep, hipStream_t s) {
+  if (!dxin || !mask || !dw || B <= 0 || H <= 0 || W <= 0 || MH <= 0 || MW <= 0 || cx < 0 || ld < cx + cmo) return -1;
   if (cmo < 1 || cmo > 16 || cmi < 1 || cmi > 255) return -1;
   const int slot = cw_slot();
   sdmi_rt::launch(cond_wgrad_kernel<CMAP>, dim3(cmo * cmi, CW_SPLITS), dim3(NT), 0, s, (const bf16_t*)dxin, ld, cx,
@@ -235,15 +236,16 @@ __global__ void time_embedding_kernel(const long long* t, int tstride, int B, in
 __global__ void silu_kernel(const bf16_t* x, const bf16_t* dy, bf16_t* y, long long n) {
   for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
     float v = bf2f(x[i]);
-    y[i] = dy ? f2bf(bf2f(dy[i]) * silu_grad_f(v)) : f2bf(silu_f(v));
+    y[i] = dy ? f2bf(bf2f(dy[i]) * silu_grad_wide_f(v)) : f2bf(silu_wide_f(v));
   }
 }
 
-// ReLU on fp32 (the leaf path's nn.ReLU, transformer.py:72,80): y = max(x, 0); with dy: dx = dy where x > 0
+// ReLU on fp32 (the leaf path's nn.ReLU, transformer.py:72,80): y = x <= 0 ? +0 : x, so a NaN stays a NaN as in
+// torch's relu; with dy: dx = x <= 0 ? 0 : dy (aten's threshold_backward: a NaN x passes dy through)
 __global__ void relu_kernel(const float* x, const float* dy, float* y, long long n) {
   for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
     const float v = x[i];
-    y[i] = dy ? (v > 0.f ? dy[i] : 0.f) : (v > 0.f ? v : 0.f);
+    y[i] = v <= 0.f ? 0.f : (dy ? dy[i] : v);
   }
 }
 
@@ -426,6 +428,8 @@ extern "C" int sdmi_pack_transpose(const sdmi_tpack_desc* descs_dev, const void*
 extern "C" int sdmi_prep_input(const float* x, int B, int cx, int H, int W, const float* mask, int cmi, int MH, int MW,
                                const float* wcond, int cmo, void* out, int cpad, const float* keep,
                                sdmi_stream_t stream) {
+  if (!x || !out || B <= 0 || cx <= 0 || H <= 0 || W <= 0 || cpad <= 0) return -1;
+  if (mask && (!wcond || cmi <= 0 || MH <= 0 || MW <= 0 || cmo <= 0)) return -1;
   if (cpad % 8 || cx + (mask ? cmo : 0) > cpad || cpad > 16) return -1;
   sdmi_rt::launch(prep_input_kernel<false>, dim3(prep_grid((long long)B * H * W)), dim3(PREP_NT), 0, (hipStream_t)stream, x,
                      B, cx, H, W, mask, cmi, MH, MW, wcond, cmo, (bf16_t*)out, cpad, keep);
@@ -436,6 +440,8 @@ extern "C" int sdmi_prep_input(const float* x, int B, int cx, int H, int W, cons
 extern "C" int sdmi_prep_input_cmap(const float* x, int B, int cx, int H, int W, const unsigned char* cmap, int cmi,
                                     int MH, int MW, const float* wcond, int cmo, void* out, int cpad, const float* keep,
                                     sdmi_stream_t stream) {
+  if (!x || !out || B <= 0 || cx <= 0 || H <= 0 || W <= 0 || cpad <= 0) return -1;
+  if (cmap && (!wcond || MH <= 0 || MW <= 0 || cmo <= 0)) return -1;
   if (cpad % 8 || cx + (cmap ? cmo : 0) > cpad || cpad > 16 || cmi < 1 || cmi > 255) return -1;
   sdmi_rt::launch(prep_input_kernel<true>, dim3(prep_grid((long long)B * H * W)), dim3(PREP_NT), 0, (hipStream_t)stream, x,
                      B, cx, H, W, cmap, cmi, MH, MW, wcond, cmo, (bf16_t*)out, cpad, keep);
@@ -456,6 +462,7 @@ extern "C" int sdmi_cond_wgrad_cmap(const void* dxin, int ld, int cx, int B, int
 
 extern "C" int sdmi_nhwc_to_nchw(const void* src, int src_f32, int ld, int B, int C, int HW, float* dst,
                                  sdmi_stream_t stream) {
+  if (!src || !dst || B <= 0 || C <= 0 || HW <= 0 || ld < C) return -1;
   sdmi_rt::launch(nhwc_to_nchw_kernel, dim3(grid_for((long long)B * C * HW)), dim3(NT), 0, (hipStream_t)stream, src,
                      src_f32, ld, B, C, HW, dst);
   SDMI_CHECK_LAUNCH();
@@ -463,6 +470,7 @@ extern "C" int sdmi_nhwc_to_nchw(const void* src, int src_f32, int ld, int B, in
 }
 
 extern "C" int sdmi_nchw_to_nhwc_bf16(const float* src, int B, int C, int HW, void* dst, int ld, sdmi_stream_t stream) {
+  if (!src || !dst || B <= 0 || C <= 0 || HW <= 0 || ld < C) return -1;
   sdmi_rt::launch(nchw_to_nhwc_bf16_kernel, dim3(grid_for((long long)B * HW * ld)), dim3(NT), 0, (hipStream_t)stream,
                      src, B, C, HW, (bf16_t*)dst, ld);
   SDMI_CHECK_LAUNCH();
@@ -483,6 +491,7 @@ extern "C" size_t sdmi_mse_workspace(void) { return 1024 * sizeof(float); }
 
 extern "C" int sdmi_mse(const float* pred, int ld, const float* target, int B, int C, int HW, float gscale,
                         const float* gscale_dev, void* grad, float* ws, float* loss, sdmi_stream_t stream) {
+  if (!pred || !target || !ws || !loss || B <= 0 || C <= 0 || HW <= 0 || ld < C) return -1;
   hipStream_t s = (hipStream_t)stream;
   int blocks = grid_for((long long)B * HW * ld);
   if (blocks > 1024) blocks = 1024;
@@ -497,7 +506,7 @@ extern "C" int sdmi_mse(const float* pred, int ld, const float* target, int B, i
 
 extern "C" int sdmi_time_embedding(const long long* t, int tstride, int B, int dim, void* out, int ld, float* out_f32,
                                    sdmi_stream_t stream) {
-  if (dim % 2) return -1;
+  if (!t || !out || B <= 0 || dim <= 0 || dim % 2 || ld < dim || tstride < 0) return -1;
   sdmi_rt::launch(time_embedding_kernel, dim3(grid_for((long long)B * dim / 2)), dim3(NT), 0, (hipStream_t)stream, t,
                      tstride, B, dim, (bf16_t*)out, ld, out_f32);
   SDMI_CHECK_LAUNCH();
@@ -505,6 +514,7 @@ extern "C" int sdmi_time_embedding(const long long* t, int tstride, int B, int d
 }
 
 extern "C" int sdmi_silu(const void* x, const void* dy, void* y, long long n, sdmi_stream_t stream) {
+  if (!x || !y || n <= 0) return -1;
   sdmi_rt::launch(silu_kernel, dim3(grid_for(n)), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x,
                      (const bf16_t*)dy, (bf16_t*)y, n);
   SDMI_CHECK_LAUNCH();
@@ -521,6 +531,7 @@ extern "C" int sdmi_relu(const float* x, const float* dy, float* y, long long n,
 
 extern "C" int sdmi_copy_slice(const void* src, int lds, void* dst, int ldd, long long P, int C, int accumulate,
                                sdmi_stream_t stream) {
+  if (!src || !dst || P <= 0 || C <= 0 || lds < C || ldd < C) return -1;
   if (C % 8 || lds % 8 || ldd % 8) return -1;
   sdmi_rt::launch(copy_slice_kernel, dim3(grid_for(P * C / 8)), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)src,
                      lds, (bf16_t*)dst, ldd, P, C, accumulate);
