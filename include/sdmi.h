@@ -379,6 +379,48 @@ int sdmi_latent_noise_bwd(const void* dzin, int ld_dzin, const float* w_post, co
                           float* r, sdmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Latent interface of the KL autoencoder (models/vae.py:96-100) and its closed-form KL term:
+ *     moments = pre_quant_conv(h), mean = moments[:, :z], logvar = moments[:, z:], sample = mean + exp(0.5 logvar) eps,
+ *     KL = (1 / B) sum_b 0.5 sum_{c,h,w} (exp(logvar) + mean^2 - 1 - logvar).
+ * z = z_channels, M = 2z <= 8 moment channels, P = B*HW pixels, P*M < 2^31. h is NHWC fp32 [P][ldh] (encoder_conv_out's
+ * output, M valid channels); moments (B,M,HW), sample / eps / dsample_add (B,z,HW) and dmom_add / dmom (B,M,HW) are
+ * contiguous NCHW fp32. No atomics, every sum in a fixed order: a second call repeats every bit. fl() = one fp32 rounding.
+ *  sdmi_kl_sample: moments[co] = the fma chain from b_pre[co] (0 when b_pre is NULL) over ci ascending of w_pre[co][ci]
+ *                  h[ci], fp32 throughout. std = expf(fl(0.5 logvar)); sample = fl(mean + fl(std eps)), nothing
+ *                  contracted; eps == NULL: sample = mean. zin != NULL: the same launch writes post_quant_conv(sample) as
+ *                  NHWC bf16 [P][ld] with the arithmetic of sdmi_pointwise_in (fma chain from the bias, ci ascending,
+ *                  RNE, pad columns zero) and replaces that launch; zin without w_post returns -1. kl != NULL (needs
+ *                  ws, sdmi_kl_workspace(P) bytes): term = fl(fl(fl(expf(logvar) + fl(mean mean)) - 1) - logvar), added
+ *                  per thread in grid-stride order with channels ascending, then the butterfly, the four waves in order,
+ *                  one partial per workgroup, and a finaliser launch: kl = fl(fl(0.5 S) / B). Launches: 1, or 2 with kl.
+ *  sdmi_kl_bwd   : with c = fl(kw / B), kw = kl_weight (times loss_w[0] when the device scalar loss_w is given):
+ *                    g       = W_post^T dzin (fma chain from 0, co ascending; 0 when dzin is NULL), then
+ *                              fl(g + dsample_add) when given
+ *                    dmean   = g, then fl(. + dmom_add_mean) when given, then fl(. + fl(c mean)) when c != 0
+ *                    dlogvar = fl(fl(fl(g eps) 0.5) std) (0 when eps is NULL), then fl(. + dmom_add_logvar) when given,
+ *                              then fl(. + fl(fl(c 0.5) fl(expf(logvar) - 1))) when c != 0
+ *                    dh[ci]  = fma chain from 0 over co ascending of w_pre[co][ci] dmom[co], RNE to bf16, NHWC [P][ld_out],
+ *                              pad columns zero: the gradient encoder_conv_out's backward consumes
+ *                  and dW_post = sum_p dzin (x) sample, db_post = sum_p dzin, dW_pre = sum_p dmom (x) h, db_pre = sum_p
+ *                  dmom through per-workgroup partials (ws, sdmi_kl_bwd_workspace() bytes) and a finisher that adds them
+ *                  in workgroup order. Every output given is fully overwritten. Nullable: dzin (then no dw_post /
+ *                  db_post), eps, h (then no dw_pre), w_pre (then no dh), loss_w, dsample_add, dmom_add and every
+ *                  output, dmom (the fp32 NCHW gradient of the moments) among them; at least one output is required.
+ *                  Launches: 2.
+ * Guard clauses return -1 before any launch: a NULL required pointer, a non-positive size, 2z > 8, a leading dimension
+ * below its channel count.
+ * ------------------------------------------------------------------------------------------- */
+size_t sdmi_kl_workspace(long long pixels);
+size_t sdmi_kl_bwd_workspace(void);
+int sdmi_kl_sample(const float* h, int ldh, const float* w_pre, const float* b_pre, const float* eps, int B, int z,
+                   int HW, float* moments, float* sample, const float* w_post, const float* b_post, void* zin, int ld,
+                   float* ws, float* kl, sdmi_stream_t stream);
+int sdmi_kl_bwd(const void* dzin, int ld_dzin, const float* w_post, const float* sample, const float* moments,
+                const float* eps, const float* h, int ldh, const float* w_pre, int B, int z, int HW, float kl_weight,
+                const float* loss_w, const float* dsample_add, const float* dmom_add, void* dh, int ld_out, float* dmom,
+                float* ws, float* dw_post, float* db_post, float* dw_pre, float* db_pre, sdmi_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * LPIPS perceptual loss (models/lpips.py) around the VGG16 convolutions (sdmi_gemm, act 2 / 3). NHWC bf16
  * activations, fp32 arithmetic, fixed-order reductions (bitwise repeatable, no atomics).
  *  sdmi_lpips_prep       : ScalingLayer + packing. out [2B*H*W][8] bf16 = (x - shift[c]) / scale[c] of in0 (rows

@@ -154,6 +154,11 @@ SIGNATURES = {
     "sdmi_latent_range": ([_P, _L, _P, _P], _I),
     "sdmi_latent_noise_fwd": ([_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _I, _P, _I, _P], _I),
     "sdmi_latent_noise_bwd": ([_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P], _I),
+    "sdmi_kl_workspace": ([_L], _SZ),
+    "sdmi_kl_bwd_workspace": ([], _SZ),
+    "sdmi_kl_sample": ([_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P], _I),
+    "sdmi_kl_bwd": ([_P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P,
+                     _P], _I),
     "sdmi_ddpm_prev": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _P], _I),
     "sdmi_ddim_prev": ([_P, _P, _P, _L, _F, _F, _F, _P, _P], _I),
     "sdmi_ddim_prev_dev": ([_P, _P, _P, _L, _P, _P, _P, _P, _P, _F, _P, _I, _P], _I),

@@ -663,3 +663,27 @@ def latent_noise_bwd(dzin, ld_dzin, w_post, dz_add, eps, z, B, C, HW, n_scale, w
                                            float(n_scale), _p(ws_range), _p(ws), _p(r), _stream()),
           "sdmi_latent_noise_bwd")
     return r
+
+
+def kl_sample(h, ldh, w_pre, b_pre, eps, B, z, HW, moments, sample, *, w_post=None, b_post=None, zin=None, ld=0, kl=None):
+    """moments = pre_quant_conv(h) (h NHWC fp32 [P][ldh]), sample = mean + exp(0.5 logvar) eps (the mean without eps);
+    with zin also post_quant_conv(sample) as the NHWC bf16 operand of decoder_conv_in, with kl (1,) the KL term (one
+    more launch, the finaliser)."""
+    ws = None
+    if kl is not None:
+        ws = torch.empty(max(_lib.lib().sdmi_kl_workspace(B * HW) // 4, 1), dtype=torch.float32, device=moments.device)
+    check(_lib.lib().sdmi_kl_sample(_p(h), ldh, _p(w_pre), _p(b_pre), _p(eps), B, z, HW, _p(moments), _p(sample),
+                                    _p(w_post), _p(b_post), _p(zin), ld, _p(ws), _p(kl), _stream()), "sdmi_kl_sample")
+    return sample, moments
+
+
+def kl_bwd(dzin, ld_dzin, w_post, sample, moments, eps, h, ldh, w_pre, B, z, HW, *, kl_weight=0.0, loss_w=None,
+           dsample_add=None, dmom_add=None, dh=None, ld_out=0, dmom=None, dw_post=None, db_post=None, dw_pre=None,
+           db_pre=None):
+    """The backward of kl_sample (and of kl_weight * KL): dh (NHWC bf16, into encoder_conv_out's backward) and / or
+    dmom (NCHW fp32), and the four 1x1-conv parameter gradients."""
+    ws = torch.empty(_lib.lib().sdmi_kl_bwd_workspace() // 4, dtype=torch.float32, device=moments.device)
+    check(_lib.lib().sdmi_kl_bwd(_p(dzin), ld_dzin, _p(w_post), _p(sample), _p(moments), _p(eps), _p(h), ldh,
+                                 _p(w_pre), B, z, HW, float(kl_weight), _p(loss_w), _p(dsample_add), _p(dmom_add),
+                                 _p(dh), ld_out, _p(dmom), _p(ws), _p(dw_post), _p(db_post), _p(dw_pre), _p(db_pre),
+                                 _stream()), "sdmi_kl_bwd")

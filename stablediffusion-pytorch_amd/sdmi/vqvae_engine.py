@@ -17,19 +17,27 @@ from .unet_engine import PackPlan
 
 
 def vqvae_layout(cfg):
+    """K (the codebook size) is None for a config without one: the KL autoencoder (sdmi.vae_engine) has no codebook."""
     return dict(down=list(cfg["down_channels"]), mid=list(cfg["mid_channels"]), ds=list(cfg["down_sample"]),
                 attn=list(cfg["attn_down"]), n_down=cfg["num_down_layers"], n_mid=cfg["num_mid_layers"],
-                n_up=cfg["num_up_layers"], z=cfg["z_channels"], K=cfg["codebook_size"], G=cfg["norm_channels"],
+                n_up=cfg["num_up_layers"], z=cfg["z_channels"], K=cfg.get("codebook_size"), G=cfg["norm_channels"],
                 heads=cfg["num_heads"])
 
 
 class VQVAEEngine:
+    def _check_latent(self):
+        if self.L["z"] > 8:
+            raise ValueError("z_channels > 8 is not supported by sdmi_vq_quantize")
+
+    def _n_lat(self):
+        """Channels encoder_conv_out stores: z here, the 2z moments in the KL autoencoder."""
+        return self.L["z"]
+
     def __init__(self, cfg, params, im_channels=3):
         self.cfg = cfg
         self.L = vqvae_layout(cfg)
         L = self.L
-        if L["z"] > 8:
-            raise ValueError("z_channels > 8 is not supported by sdmi_vq_quantize")
+        self._check_latent()
         for c in L["down"] + L["mid"]:
             if c % 8:
                 raise ValueError("channel counts must be multiples of 8")
@@ -175,11 +183,9 @@ class VQVAEEngine:
         return out
 
     # ------------------------------------------------------------------------------------------
-    def encode(self, x, want_pre_quant=False, n_scale=0.0, eps=None):
-        """vqvae.py:128-139. x: (B, 3, H, W) fp32 -> (z_q NCHW fp32, loss (1,), indices int64 (B, h, w)
-        [, pre-quantisation latent NCHW fp32]). n_scale != 0 (vqvae_noise.py:155): the returned z_q is z_q +
-        (max - min) n_scale eps, eps (z_q's shape, fp32) the caller's standard-normal draw; the loss and the indices
-        are the clean latent's."""
+    def _encoder(self, x):
+        """vqvae.py:128-136, the encoder up to encoder_conv_out: x (B, 3, H, W) fp32 -> (NHWC fp32 [B*h*w][8] with
+        _n_lat() valid channels, h, w)."""
         L, P = self.L, self.P
         B, Cx, H, W = x.shape
         assert Cx == self.im_channels
@@ -208,7 +214,16 @@ class VQVAEEngine:
         m = L["mid"]
         for i in range(len(m) - 1):
             cur = self._mid(f"encoder_mids.{i}", cur, B, h, w, m[i], m[i + 1])
-        z = self._head("encoder_norm_out", "encoder_conv_out", cur, B, h, w, d[-1], L["z"])
+        return self._head("encoder_norm_out", "encoder_conv_out", cur, B, h, w, d[-1], self._n_lat()), h, w
+
+    def encode(self, x, want_pre_quant=False, n_scale=0.0, eps=None):
+        """vqvae.py:128-139. x: (B, 3, H, W) fp32 -> (z_q NCHW fp32, loss (1,), indices int64 (B, h, w)
+        [, pre-quantisation latent NCHW fp32]). n_scale != 0 (vqvae_noise.py:155): the returned z_q is z_q +
+        (max - min) n_scale eps, eps (z_q's shape, fp32) the caller's standard-normal draw; the loss and the indices
+        are the clean latent's."""
+        L, P = self.L, self.P
+        B = x.shape[0]
+        z, h, w = self._encoder(x)
         zq = torch.empty(B, L["z"], h, w, dtype=torch.float32, device=self.device)
         idx = torch.empty(B, h, w, dtype=torch.int64, device=self.device)
         pre = torch.empty_like(zq) if want_pre_quant else None

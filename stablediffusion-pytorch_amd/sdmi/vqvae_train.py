@@ -33,13 +33,19 @@ class VQVAETrainEngine(UNetEngine):
 
     _group_wg = False  # its own backward loop issues every weight gradient in place (no per-block grouping)
 
+    def _check_latent(self):
+        if self.L["z"] > 8:
+            raise ValueError("z_channels > 8 is not supported by sdmi_vq_quantize")
+
+    def _n_lat(self):
+        """Channels encoder_conv_out stores (and its weight gradient's rows): z here, 2z in the KL autoencoder."""
+        return self.L["z"]
+
     def __init__(self, cfg, params, grads=None, im_channels=3):
-        import os
         self.cfg = cfg
         self.L = vqvae_layout(cfg)
         L = self.L
-        if L["z"] > 8:
-            raise ValueError("z_channels > 8 is not supported by sdmi_vq_quantize")
+        self._check_latent()
         for c in L["down"] + L["mid"]:
             if c % 8:
                 raise ValueError("channel counts must be multiples of 8")
@@ -118,11 +124,15 @@ class VQVAETrainEngine(UNetEngine):
         return (B, self.L["z"], H // f, W // f)
 
     def forward(self, x, need_backward=True, n_scale=0.0, eps=None):
+        return self._forward(x, need_backward, dict(n_scale=n_scale, eps=eps))
+
+    def _forward(self, x, need_backward, latent):
         """x: (B, im_channels, H, W) fp32 image. Returns (reconstruction NHWC fp32 [B*H*W, 8] with the first
         im_channels valid, ctx); ctx["vq_loss"] (1,) = mean((q - x)^2) (the codebook and the commitment loss share
         this value), ctx["indices"] (B, h, w) int64. n_scale != 0 (vqvae_noise.py:155): the decoder sees zq + (max -
         min) n_scale eps, eps a standard-normal fp32 tensor of latent_shape(B, H, W); ctx["z"] is that noisy latent,
-        ctx["eps"] and ctx["range_ws"] what the backward reads again, ctx["zq"] stays the clean latent."""
+        ctx["eps"] and ctx["range_ws"] what the backward reads again, ctx["zq"] stays the clean latent.
+        `latent`: the keyword arguments of _latent_fwd, the one section a subclass replaces."""
         L, P = self.L, self.P
         B, Cx, H, W = x.shape
         assert Cx == self.im_channels
@@ -168,42 +178,12 @@ class VQVAETrainEngine(UNetEngine):
         tab = K.gn_fwd(cur, B, Pn, d[-1], G, P["encoder_norm_out.weight"], P["encoder_norm_out.bias"], True, hs)
         z = self._new(B * Pn, 8, torch.float32)
         K.conv_fwd(hs, B, h, w, d[-1], d[-1], self.W("encoder_conv_out#f"), 8, 3, 3, 1, 1, z, 8,
-                   bias=P["encoder_conv_out.bias"], n_store=L["z"])
+                   bias=P["encoder_conv_out.bias"], n_store=self._n_lat())
         q = dict(B=B, h=h, w=w)  # state shared by the quantiser's backward entries
         tape.append((self._bwd_enc_out, dict(x=cur, xn=name, tab=tab, hs=hs, B=B, h=h, w=w, q=q)))
-        # ---- quantiser (vqvae.py:93-126) ----
-        zc = L["z"]
-        zq = torch.empty(B, zc, h, w, dtype=torch.float32, device=self.device)
-        pre = torch.empty_like(zq)
-        idx = torch.empty(B, h, w, dtype=torch.int64, device=self.device)
-        vq_loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        ws = torch.empty(_lib.lib().sdmi_vq_workspace(B * Pn) // 4 + 1, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().sdmi_vq_quantize(z.data_ptr(), 8, P["pre_quant_conv.weight"].data_ptr(),
-                                               P["pre_quant_conv.bias"].data_ptr(), P["embedding.weight"].data_ptr(),
-                                               L["K"], B, Pn, zc, zq.data_ptr(), idx.data_ptr(), pre.data_ptr(),
-                                               ws.data_ptr(), vq_loss.data_ptr(), K._stream()), "sdmi_vq_quantize")
-        q.update(z=z, zq=zq, pre=pre, idx=idx)
-        tape.label = "quant"
-        tape.append((self._bwd_quant, dict(q=q)))
-        # ---- decoder (vqvae.py:141-153) ----
+        # ---- latent interface (vqvae.py:93-126, 141-144) ----
+        zin, lat = self._latent_fwd(z, q, tape, **latent)
         tape.label = "decoder_in"
-        zin = self._new(B * Pn, 8)
-        noise = {}
-        if float(n_scale) != 0.0:  # range + one launch that adds the noise and applies post_quant_conv
-            if eps is None or tuple(eps.shape) != tuple(zq.shape):
-                raise ValueError("n_scale != 0 needs eps, a standard-normal draw of latent_shape(B, H, W)")
-            eps = plan.as_operand(eps)
-            zn = torch.empty_like(zq)
-            rws = K.latent_range(zq, K.latent_noise_ws(zq.numel(), self.device))
-            K.latent_noise_fwd(zq, eps, B, zc, Pn, n_scale, rws, zn, w_post=P["post_quant_conv.weight"],
-                               b_post=P["post_quant_conv.bias"], cout=zc, zin=zin, ld=8)
-            noise = dict(z=zn, eps=eps, range_ws=rws)
-            # (q["z"] is encoder_conv_out's output, the z_enc of sdmi_vq_bwd: the noisy latent goes by another name)
-            q.update(noisy=zn, eps=eps, range_ws=rws, n_scale=float(n_scale))
-        else:
-            _lib.check(_lib.lib().sdmi_pointwise_in(zq.data_ptr(), B, zc, Pn, P["post_quant_conv.weight"].data_ptr(),
-                                                    P["post_quant_conv.bias"].data_ptr(), zc, zin.data_ptr(), 8,
-                                                    K._stream()), "sdmi_pointwise_in")
         cur, name = self._new(B * Pn, m[-1]), "dec_in"
         K.conv_fwd(zin, B, h, w, 8, 8, self.W("decoder_conv_in#f"), m[-1], 3, 3, 1, 1, cur, m[-1],
                    bias=P["decoder_conv_in.bias"])
@@ -235,10 +215,50 @@ class VQVAETrainEngine(UNetEngine):
         K.conv_fwd(hs, B, h, w, d[0], d[0], self.W("decoder_conv_out#f"), 8, 3, 3, 1, 1, out, 8,
                    bias=P["decoder_conv_out.bias"], n_store=self.im_channels)
         tape.append((self._bwd_dec_out, dict(x=cur, xn=name, tab=tab, hs=hs, B=B, H=h, W=w)))
-        ctx = dict(tape=tape, st=st, grads=grads, vq_loss=vq_loss, indices=idx, zq=zq, pre_quant=pre, **noise)
+        ctx = dict(tape=tape, st=st, grads=grads, **lat)
         if not need_backward:
             ctx.pop("tape")
         return out, ctx
+
+    def _latent_fwd(self, z, q, tape, n_scale=0.0, eps=None):
+        """The quantiser (vqvae.py:93-126), the latent noise and post_quant_conv: from z (encoder_conv_out's output,
+        NHWC fp32 [P][8]) to zin (decoder_conv_in's operand, NHWC bf16 [P][8]). Appends its backward to the tape,
+        fills q (the state its backward and _bwd_dec_in / _bwd_enc_out share) and returns (zin, the ctx entries)."""
+        L, P = self.L, self.P
+        B, h, w = q["B"], q["h"], q["w"]
+        Pn = h * w
+        zc = L["z"]
+        zq = torch.empty(B, zc, h, w, dtype=torch.float32, device=self.device)
+        pre = torch.empty_like(zq)
+        idx = torch.empty(B, h, w, dtype=torch.int64, device=self.device)
+        vq_loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        ws = torch.empty(_lib.lib().sdmi_vq_workspace(B * Pn) // 4 + 1, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().sdmi_vq_quantize(z.data_ptr(), 8, P["pre_quant_conv.weight"].data_ptr(),
+                                               P["pre_quant_conv.bias"].data_ptr(), P["embedding.weight"].data_ptr(),
+                                               L["K"], B, Pn, zc, zq.data_ptr(), idx.data_ptr(), pre.data_ptr(),
+                                               ws.data_ptr(), vq_loss.data_ptr(), K._stream()), "sdmi_vq_quantize")
+        q.update(z=z, zq=zq, pre=pre, idx=idx)
+        tape.label = "quant"
+        tape.append((self._bwd_quant, dict(q=q)))
+        tape.label = "decoder_in"
+        zin = self._new(B * Pn, 8)
+        noise = {}
+        if float(n_scale) != 0.0:  # range + one launch that adds the noise and applies post_quant_conv
+            if eps is None or tuple(eps.shape) != tuple(zq.shape):
+                raise ValueError("n_scale != 0 needs eps, a standard-normal draw of latent_shape(B, H, W)")
+            eps = plan.as_operand(eps)
+            zn = torch.empty_like(zq)
+            rws = K.latent_range(zq, K.latent_noise_ws(zq.numel(), self.device))
+            K.latent_noise_fwd(zq, eps, B, zc, Pn, n_scale, rws, zn, w_post=P["post_quant_conv.weight"],
+                               b_post=P["post_quant_conv.bias"], cout=zc, zin=zin, ld=8)
+            noise = dict(z=zn, eps=eps, range_ws=rws)
+            # (q["z"] is encoder_conv_out's output, the z_enc of sdmi_vq_bwd: the noisy latent goes by another name)
+            q.update(noisy=zn, eps=eps, range_ws=rws, n_scale=float(n_scale))
+        else:
+            _lib.check(_lib.lib().sdmi_pointwise_in(zq.data_ptr(), B, zc, Pn, P["post_quant_conv.weight"].data_ptr(),
+                                                    P["post_quant_conv.bias"].data_ptr(), zc, zin.data_ptr(), 8,
+                                                    K._stream()), "sdmi_pointwise_in")
+        return zin, dict(vq_loss=vq_loss, indices=idx, zq=zq, pre_quant=pre, **noise)
 
     def _mid(self, p, cur, name, B, h, w, cin, cout, st, tape, grads):
         """MidBlock (blocks.py:225-267 at t_emb_dim=None): resnet, then [self-attention, resnet] x num_layers."""
@@ -312,7 +332,7 @@ class VQVAETrainEngine(UNetEngine):
         dz = q["dz"]
         with self._wg(dz):
             K.conv_wgrad(dz, 8, c["hs"], B, h, w, C, C, 8, 3, 3, 1, 1, self.g("encoder_conv_out.weight"), h, w,
-                         m_store=self.L["z"], bias_grad=self.g("encoder_conv_out.bias"))
+                         m_store=self._n_lat(), bias_grad=self.g("encoder_conv_out.bias"))
         dhs = self._new(B * Pn, C)
         K.conv_fwd(dz, B, h, w, 8, 8, self.W("encoder_conv_out#d"), C, 3, 3, 1, 1, dhs, C)
         dx, fresh = grads.get(c["xn"])
@@ -339,6 +359,11 @@ class VQVAETrainEngine(UNetEngine):
         self.codebook_weight = float(codebook_weight)
         self.commitment_beta = float(commitment_beta)
         self.dzq_add, self.loss_w = dzq, loss_w
+        self._run_tape(ctx, dout, grads, on_progress)
+
+    def _run_tape(self, ctx, dout, grads=None, on_progress=None):
+        """The tape backwards from dout; the latent section's weights and outside gradients are attributes the caller
+        (backward) has set."""
         if grads is not None:
             self.Gd = grads
         assert self.Gd is not None, "engine built without gradient buffers"
@@ -361,25 +386,17 @@ def noise_key(noise_seed, rank=0):
     return (int(noise_seed) + int(rank)) & 0xFFFFFFFFFFFFFFFF
 
 
-class VQVAETrainer:
-    """The generator step of train_vqvae_celebhq.py:405-470 without the GAN term: forward, recon MSE + codebook
-    (weight codebook_weight) + commitment (commitment_beta) losses, backward, Adam(lr, betas=(0.5, 0.999)).
-    With lpips_state (an LPIPS state dict) and a non-zero perceptual_weight the step adds perceptual_weight *
-    mean_b LPIPS(out, im) (train_vqvae_celebhq.py:427-428); by default no LPIPS engine exists and the step is unchanged.
-    Flat fp32 parameter / gradient / moment buffers; the step never synchronises with the host. With N > 1 ranks
-    the gradients are averaged over the process group (one bucketed all-reduce after the backward) before Adam.
+class AutoencoderTrainer:
+    """What the autoencoder trainers share (VQVAETrainer here, sdmi.vae_train.VAETrainer): flat fp32 parameter /
+    gradient / moment buffers, the reconstruction MSE (plus the optional LPIPS term through the reconstruction gradient),
+    the bucketed all-reduce over N > 1 ranks, Adam, and the device draw sdmi_randn(key = noise_key(noise_seed, rank),
+    offset) whose offset is a device counter that advances with every draw. A subclass names its engine and supplies the
+    latent section's calls: _forward(im) -> (out, ctx), _backward(ctx, dout), _keep(ctx, out) and losses()."""
 
-    n_scale (settable attribute, default 0): the noise-robust autoencoder of train_vqvae_celebhq_noise_multi_GPU.py --
-    the decoder sees zq + (zq.max() - zq.min()) * n_scale * eps (models/vqvae_noise.py:177-183). eps is drawn on the
-    device by sdmi_randn(key = noise_key(noise_seed, rank), offset), the offset a device counter owned by the trainer
-    that advances with every draw, so every step -- and every replay of a recorded step -- draws fresh, reproducible
-    noise. n_scale is a launch argument: a recorded StepPlan keeps the value it was recorded with and must be recorded
-    again after n_scale changes (the reference's staged schedule changes it a few times per run), as guidance_scale
-    in sdmi.sampling. With n_scale == 0 nothing is allocated or launched for the noise. state_dict() is unchanged."""
+    engine_cls = None
 
-    def __init__(self, cfg, state_dict, device, *, im_channels=3, lr=2e-5, betas=(0.5, 0.999), eps=1e-8,
-                 codebook_weight=1.0, commitment_beta=0.2, group=None, bucket_bytes=64 << 20,
-                 perceptual_weight=0.0, lpips_state=None, n_scale=0.0, noise_seed=0):
+    def __init__(self, cfg, state_dict, device, *, im_channels, lr, betas, eps, group, bucket_bytes, perceptual_weight,
+                 lpips_state, noise_seed, hp):
         from .reducer import BucketReducer
         self.cfg = cfg
         self.device = torch.device(device)
@@ -396,19 +413,16 @@ class VQVAETrainer:
         self.v = torch.zeros_like(self.store.params)
         # optimizer state vector (csrc/optim.hip); loss scale 1 and no growth: the reference step is plain fp32
         self.state = torch.tensor([0, 0, 1.0, 0, 0, 0, 0, 0], dtype=torch.float32, device=self.device)
-        self.hp = dict(lr=lr, b1=betas[0], b2=betas[1], eps=eps, cw=codebook_weight, beta=commitment_beta)
-        self.engine = VQVAETrainEngine(cfg, self.store.p, self.store.g, im_channels=im_channels)
+        self.hp = dict(lr=lr, b1=betas[0], b2=betas[1], eps=eps, **hp)
+        self.engine = self.engine_cls(cfg, self.store.p, self.store.g, im_channels=im_channels)
         self.reducer = BucketReducer(self.store.grads, group, bucket_bytes) if self.world > 1 else None
         if self.reducer is not None and self.engine.side is not None:
             self.reducer.producers.append(self.engine.side)
         self.engine.refresh_weights()
-        self.vq_loss = None
-        self.indices = None
         self.lpips = None
         rank = dist.get_rank(group) if self.world > 1 else 0
         self.noise_key = noise_key(noise_seed, rank)
-        self.noise_offset = None  # the device draw counter, allocated with the first non-zero n_scale
-        self.n_scale = n_scale
+        self.noise_offset = None  # the device draw counter, allocated by whoever draws
         if perceptual_weight and lpips_state is None:
             raise ValueError("perceptual_weight is set but no LPIPS weights were given (lpips_state=)")
         if perceptual_weight and lpips_state is not None:
@@ -418,16 +432,6 @@ class VQVAETrainer:
             self.hp["pw"] = float(perceptual_weight)
             self.lpips = LPIPSEngine(lpips_state, self.device)
             self.lp_loss = torch.zeros(1, dtype=torch.float32, device=self.device)  # the weighted perceptual loss
-
-    @property
-    def n_scale(self):
-        return self._n_scale
-
-    @n_scale.setter
-    def n_scale(self, value):
-        self._n_scale = float(value)
-        if self._n_scale != 0.0 and self.noise_offset is None:
-            self.noise_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
 
     def _draw(self, shape):
         """eps ~ N(0, 1) of the latent's shape at the trainer's (key, device offset); the offset advances."""
@@ -442,10 +446,7 @@ class VQVAETrainer:
         eng, st, hp = self.engine, self.store, self.hp
         B, C, H, W = im.shape
         self._shape = (B, C, H, W)
-        if self._n_scale != 0.0:
-            out, ctx = eng.forward(im, n_scale=self._n_scale, eps=self._draw(eng.latent_shape(B, H, W)))
-        else:
-            out, ctx = eng.forward(im)
+        out, ctx = self._forward(im)
         dout = eng.new_dpred(B, H, W)
         if self.lpips is None:
             K.mse(out, 8, plan.as_operand(im), B, C, H * W, 1.0, dout, self.state[S_LOSS:S_LOSS + 1])
@@ -458,12 +459,12 @@ class VQVAETrainer:
             self.lpips.backward(lctx, None, want=(True, False), gscale=hp["pw"] / B, acc=dout, mse=(out, imo))
         if self.reducer is not None:
             self.reducer.reset()
-        eng.backward(ctx, dout, hp["cw"], hp["beta"])
+        self._backward(ctx, dout)
         if self.reducer is not None:
             self.reducer.ready(st.numel)
             self.reducer.finish()
-        self.vq_loss, self.indices, self.out = ctx["vq_loss"], ctx["indices"], out
-        self.eps, self.zq, self.z = ctx.get("eps"), ctx["zq"], ctx.get("z", ctx["zq"])
+        self.out = out
+        self._keep(ctx, out)
         L = _lib.lib()
         wsb = L.sdmi_optim_workspace_for(st.numel)
         ws = torch.empty(wsb // 4, dtype=torch.float32, device=self.device)
@@ -478,6 +479,67 @@ class VQVAETrainer:
         eng.refresh_weights()
         return self.state
 
+    def reconstruction(self):
+        """The last step's decoder output as (B, im_channels, H, W) fp32."""
+        B, C, H, W = self._shape
+        return self.engine.pred_to_nchw(self.out, B, H, W)
+
+    def state_dict(self):
+        return {k: self.store.p[k] for k in self.store.shapes}
+
+
+class VQVAETrainer(AutoencoderTrainer):
+    """The generator step of train_vqvae_celebhq.py:405-470 without the GAN term: forward, recon MSE + codebook
+    (weight codebook_weight) + commitment (commitment_beta) losses, backward, Adam(lr, betas=(0.5, 0.999)).
+    With lpips_state (an LPIPS state dict) and a non-zero perceptual_weight the step adds perceptual_weight *
+    mean_b LPIPS(out, im) (train_vqvae_celebhq.py:427-428); by default no LPIPS engine exists and the step is unchanged.
+    Flat fp32 parameter / gradient / moment buffers; the step never synchronises with the host. With N > 1 ranks
+    the gradients are averaged over the process group (one bucketed all-reduce after the backward) before Adam.
+
+    n_scale (settable attribute, default 0): the noise-robust autoencoder of train_vqvae_celebhq_noise_multi_GPU.py --
+    the decoder sees zq + (zq.max() - zq.min()) * n_scale * eps (models/vqvae_noise.py:177-183). eps is drawn on the
+    device by sdmi_randn(key = noise_key(noise_seed, rank), offset), the offset a device counter owned by the trainer
+    that advances with every draw, so every step -- and every replay of a recorded step -- draws fresh, reproducible
+    noise. n_scale is a launch argument: a recorded StepPlan keeps the value it was recorded with and must be recorded
+    again after n_scale changes (the reference's staged schedule changes it a few times per run), as guidance_scale
+    in sdmi.sampling. With n_scale == 0 nothing is allocated or launched for the noise. state_dict() is unchanged."""
+
+    engine_cls = VQVAETrainEngine
+
+    def __init__(self, cfg, state_dict, device, *, im_channels=3, lr=2e-5, betas=(0.5, 0.999), eps=1e-8,
+                 codebook_weight=1.0, commitment_beta=0.2, group=None, bucket_bytes=64 << 20,
+                 perceptual_weight=0.0, lpips_state=None, n_scale=0.0, noise_seed=0):
+        super().__init__(cfg, state_dict, device, im_channels=im_channels, lr=lr, betas=betas, eps=eps, group=group,
+                         bucket_bytes=bucket_bytes, perceptual_weight=perceptual_weight, lpips_state=lpips_state,
+                         noise_seed=noise_seed, hp=dict(cw=codebook_weight, beta=commitment_beta))
+        self.vq_loss = None
+        self.indices = None
+        self.n_scale = n_scale  # (allocates the draw counter with the first non-zero value)
+
+    @property
+    def n_scale(self):
+        return self._n_scale
+
+    @n_scale.setter
+    def n_scale(self, value):
+        self._n_scale = float(value)
+        if self._n_scale != 0.0 and self.noise_offset is None:
+            self.noise_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def _forward(self, im):
+        eng = self.engine
+        B, _, H, W = im.shape
+        if self._n_scale != 0.0:
+            return eng.forward(im, n_scale=self._n_scale, eps=self._draw(eng.latent_shape(B, H, W)))
+        return eng.forward(im)
+
+    def _backward(self, ctx, dout):
+        self.engine.backward(ctx, dout, self.hp["cw"], self.hp["beta"])
+
+    def _keep(self, ctx, out):
+        self.vq_loss, self.indices = ctx["vq_loss"], ctx["indices"]
+        self.eps, self.zq, self.z = ctx.get("eps"), ctx["zq"], ctx.get("z", ctx["zq"])
+
     def losses(self):
         """Host dict of the last step's losses (synchronises): recon, codebook (weighted), commitment (weighted) and,
         with the LPIPS term, perceptual (weighted)."""
@@ -489,11 +551,3 @@ class VQVAETrainer:
             d["perceptual"] = self.lp_loss.item()
             d["total"] += d["perceptual"]
         return d
-
-    def reconstruction(self):
-        """The last step's decoder output as (B, im_channels, H, W) fp32."""
-        B, C, H, W = self._shape
-        return self.engine.pred_to_nchw(self.out, B, H, W)
-
-    def state_dict(self):
-        return {k: self.store.p[k] for k in self.store.shapes}
