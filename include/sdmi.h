@@ -434,15 +434,22 @@ int sdmi_kl_bwd(const void* dzin, int ld_dzin, const float* w_post, const float*
  *                          and rounded once, channels 3..7 zero.
  *  sdmi_maxpool2_fwd/bwd : nn.MaxPool2d(2, 2) on (N,H,W,C) bf16, C % 8 == 0, floor mode. The backward recomputes the
  *                          argmax from x (first maximum in window scan order, as torch) and fully overwrites dx (the
- *                          dropped odd row / column gets zero).
+ *                          dropped odd row / column gets zero). A NaN replaces the running maximum (v > m ||
+ *                          isnan(v), as torch): any NaN in a window gives NaN and takes the gradient (the last one).
  *  sdmi_lpips_dist_fwd   : one tap f [2B*P][ld] (C in {64,128,256,512}): u = f / max(|f|, 1e-12) per pixel,
  *                          val[b] (+)= (1/P) sum_p sum_c w[c] (u0 - u1)^2 (accumulate = 0 overwrites). rn (nullable):
  *                          the 2B*P inverse norms the backward needs. ws: sdmi_lpips_dist_workspace(B, P, C) bytes.
  *  sdmi_lpips_dist_bwd   : gradient of the rows of image `side` (0 / 1), B*P rows into dy: df = coef rn_a (t - u_a
  *                          sum_k t_k u_a,k), t_c = 2 w_c (u_a,c - u_o,c), coef = (g ? g[b] : 1) * gscale / P;
- *                          dy = f > 0 ? df + addend : 0 (addend nullable: the gradient from the next slice). Rows
- *                          that are all zero give exact zeros.
+ *                          dy = f <= 0 ? 0 : df + addend (addend nullable: the gradient from the next slice; a NaN
+ *                          activation passes it on, as torch's threshold_backward). Rows that are all zero give exact
+ *                          zeros.
  *  sdmi_lpips_mean       : out[0] = scale * sum_b val[b].
+ * NaN passes through the whole chain as in torch (the convolutions' act 2 / 3 epilogues included): an image with a NaN
+ * pixel gets a NaN val. Each entry point returns -1 before any launch for a null required pointer, a non-positive size,
+ * C outside {64,128,256,512} (distance) or not a positive multiple of 8 (pool), H or W < 2 (pool), ld / ld_dy / ld_add
+ * below C or not a multiple of 8, side outside {0, 1}, B > 65535 (distance), and for sdmi_lpips_image_grad neither
+ * output, one of mse_pred / mse_target alone, or mse without acc_nhwc. sdmi_lpips_dist_workspace returns 0 then.
  * ------------------------------------------------------------------------------------------- */
 int sdmi_lpips_prep(const float* in0, int in0_nhwc, const float* in1, int in1_nhwc, int B, int H, int W,
                     const float* shift, const float* scale, int normalize, void* out, sdmi_stream_t stream);

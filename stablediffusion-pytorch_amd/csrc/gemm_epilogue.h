@@ -13,11 +13,12 @@ __device__ __forceinline__ long long rb_row(const EpiArgs& g, int row) {
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int CPOL_SC1 = 16;  // buffer cache policy: device (agent) scope coherence
 
-// activation of the epilogue: 1 SiLU, 2 ReLU, 3 ReLU gradient (keep v where aux > 0)
+// activation of the epilogue: 1 SiLU, 2 ReLU, 3 ReLU gradient (v unless aux <= 0). A NaN passes both, as in torch's
+// relu and threshold_backward: 2 gives NaN for a NaN v, 3 keeps v under a NaN aux.
 __device__ __forceinline__ float act1(const EpiArgs& g, float v, long long orow, int col) {
   if (g.act == 1) return silu_f(v);
-  if (g.act == 2) return fmaxf(v, 0.f);
-  if (g.act == 3) return bf2f(g.aux[orow * g.ld_aux + col]) > 0.f ? v : 0.f;
+  if (g.act == 2) return v <= 0.f ? 0.f : v;
+  if (g.act == 3) return bf2f(g.aux[orow * g.ld_aux + col]) <= 0.f ? 0.f : v;
   return v;
 }
 
@@ -96,12 +97,12 @@ struct Epi {
       for (int e = 0; e < 8; ++e) v[e] = silu_f(v[e]);
     } else if (g.act == 2) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+      for (int e = 0; e < 8; ++e) v[e] = v[e] <= 0.f ? 0.f : v[e];
     } else if (g.act == 3) {
       float t[8];
       unpack8(*(const uint4*)(g.aux + orow * g.ld_aux + col), t);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = t[e] > 0.f ? v[e] : 0.f;
+      for (int e = 0; e < 8; ++e) v[e] = t[e] <= 0.f ? 0.f : v[e];
     }
     if (g.c_f32) {
       float* d = (float*)g.C + orow * g.ldc + col;

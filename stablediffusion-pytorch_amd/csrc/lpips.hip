@@ -3,6 +3,12 @@
 // spatial mean) with its backward, and the image gradient out of the scaled-image gradient.
 // Activations are NHWC bf16 (16 bytes = 8 channels per access), arithmetic fp32. Every reduction has a fixed order
 // (lanes, waves, per-block partials, one ordered sum): results are bitwise repeatable, no atomics.
+// NaN passes as in torch: through the pool pair (below), through the ReLU select of the distance backward, and -- in
+// the GEMM epilogue of the convolutions (gemm_epilogue.h, act 2 and 3) -- through ReLU and its gradient; an image with a
+// NaN pixel gets a NaN distance. Every entry point returns -1 before any launch for a null required pointer, a
+// non-positive size, C outside {64, 128, 256, 512} (distance) or not a positive multiple of 8 (pool), H or W below 2
+// (pool), a leading dimension below C or not a multiple of 8, side outside {0, 1}, B above 65535 (distance: grid.y), and
+// for the image gradient no output, one of mse_pred / mse_target alone, or mse without acc_nhwc.
 #include "common.h"
 #include "../../include/sdmi.h"
 
@@ -89,7 +95,8 @@ __global__ void lpips_image_grad_kernel(const bf16_t* d, int B, int HW, const fl
 
 // ---------------------------------------------------------------------------------------------
 // nn.MaxPool2d(2, 2) on NHWC bf16, floor mode. The first maximum in scan order (0,0), (0,1), (1,0), (1,1) wins
-// (strict > while scanning), as torch's forward records its index.
+// (strict > while scanning), as torch's forward records its index. A NaN replaces the running maximum as it does in
+// torch (v > m || isnan(v)): any NaN in the window gives NaN, and the gradient goes to the last NaN in scan order.
 // ---------------------------------------------------------------------------------------------
 __global__ void maxpool2_fwd_kernel(const bf16_t* x, int N, int H, int W, int C, bf16_t* y) {
   const int OH = H >> 1, OW = W >> 1, CG = C >> 3;
@@ -108,7 +115,7 @@ __global__ void maxpool2_fwd_kernel(const bf16_t* x, int N, int H, int W, int C,
     for (int k = 1; k < 4; ++k) {
       unpack8(*(const uint4*)(px + ((long long)(k >> 1) * W + (k & 1)) * C), v);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) m[e] = v[e] > m[e] ? v[e] : m[e];
+      for (int e = 0; e < 8; ++e) m[e] = (v[e] > m[e] || v[e] != v[e]) ? v[e] : m[e];
     }
     *(uint4*)(y + i * 8) = pack8(m);
   }
@@ -144,7 +151,7 @@ __global__ void maxpool2_bwd_kernel(const bf16_t* x, const bf16_t* dy, int N, in
       unpack8(*(const uint4*)(x + base + ((long long)(k >> 1) * W + (k & 1)) * C), v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const bool gt = v[e] > m[e];
+        const bool gt = v[e] > m[e] || v[e] != v[e];
         m[e] = gt ? v[e] : m[e];
         arg[e] = gt ? k : arg[e];
       }
@@ -239,12 +246,14 @@ __global__ void lpips_dist_sum_kernel(const float* partial, int nblk, float inv_
   float acc = 0.f;
   for (int i = threadIdx.x; i < nblk; i += 64) acc += partial[(long long)b * nblk + i];
   acc = wave_sum(acc);
-  if (threadIdx.x == 0) val[b] = (accumulate ? val[b] : 0.f) + acc * inv_p;
+  // one rounding, stated (the compiler contracted the plain expression to the same fma)
+  if (threadIdx.x == 0) val[b] = fmaf(acc, inv_p, accumulate ? val[b] : 0.f);
 }
 
 // Gradient of the tap rows of image `side` (a: own rows, o: the other image's):
 //   t_c = 2 w_c (ua_c - uo_c),  df_c = coef * rn_a * (t_c - ua_c * sum_k t_k ua_k),  coef = (g ? g[b] : 1) * gscale / P
-//   dy = f_a > 0 ? df + addend : 0   (the tap is a ReLU output; addend: the gradient arriving from the next slice)
+//   dy = f_a <= 0 ? 0 : df + addend   (the tap is a ReLU output; addend: the gradient arriving from the next slice;
+//   a NaN activation passes the gradient on, as torch's threshold_backward does)
 // An all-zero row has u = 0 and a huge rn; the select keeps its output an exact zero.
 __global__ void lpips_dist_bwd_kernel(const bf16_t* f, int ld, const float* w, const float* rn, const float* g,
                                       float gscale, int B, int P, int C, int side, const bf16_t* addend, int ld_add,
@@ -288,7 +297,7 @@ __global__ void lpips_dist_bwd_kernel(const bf16_t* f, int ld, const float* w, c
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float df = coef * ia * (t[e] - a[e] * ia * s);
-      out[e] = a[e] > 0.f ? df + ad[e] : 0.f;
+      out[e] = a[e] <= 0.f ? 0.f : df + ad[e];
     }
     if (ok) *(uint4*)(dy + r * ld_dy + cl * 8) = pack8(out);
   }

@@ -271,3 +271,58 @@ def test_conv_dgrad_relu_mask_exact(case):
     torch.cuda.synchronize()
     assert torch.equal(out.view.cpu(), GM.to_c(ref, BF))
     assert out.outside_untouched()
+
+
+def _same_with_nan(got, ref):
+    n = torch.isnan(ref)
+    return torch.equal(torch.isnan(got), n) and torch.equal(got[~n], ref[~n])
+
+
+@pytest.mark.parametrize("pad", [8, 4], ids=["vec", "scalar"])
+@pytest.mark.parametrize("case", ["conv1_1", "c64", "c128_ragged"])
+def test_conv_bias_relu_passes_nan(case, pad):
+    """act 2 is torch's relu: a NaN accumulator stays NaN after the bias (v <= 0 ? 0 : v, not fmaxf(v, 0), which
+    returns 0). One NaN planted in the input reaches the 3x3 neighbourhood of its pixel in every output channel;
+    everything else is the exact integer result of test_conv_bias_relu_exact. pad: the output's row stride is
+    cout + pad -- a multiple of 8 takes the 8-wide epilogue (Epi::finish8), cout + 4 the per-element one (act1)."""
+    K = _k()
+    B, H, W, cin, cout = {"conv1_1": (2, 9, 7, 3, 64), "c64": (2, 6, 10, 64, 128), "c128_ragged": (1, 5, 5, 128, 256)}[case]
+    x, w, flat = _int_conv(B, H, W, cin, cout, 41)
+    x[B - 1, cin - 1, 2, 3] = float("nan")
+    bias = GM.ints((cout,), 43).to(F32)
+    ref = flat(F.relu(F.conv2d(x, w, bias.double(), padding=1)))
+    assert int(torch.isnan(ref).sum()) == 9 * cout and not torch.isnan(ref).all()
+    cp = 8 if cin == 3 else cin
+    xp = F.pad(flat(x), (0, cp - cin))
+    wpk = F.pad(w.permute(0, 2, 3, 1), (0, cp - cin)).reshape(cout, 9 * cp)
+    xg, wg = GM.place(xp, cp, DEV), GM.place(wpk, 9 * cp, DEV)
+    out = GM.Guarded(B * H * W, cout, cout + pad, BF, DEV)
+    K.conv_fwd(xg.view, B, H, W, cp, cp, wg.view, cout, 3, 3, 1, 1, out.view, cout + pad, bias=bias.to(DEV), act=2)
+    torch.cuda.synchronize()
+    assert _same_with_nan(out.view.cpu().double(), GM.to_c(ref, BF).double())
+    assert out.outside_untouched()
+
+
+@pytest.mark.parametrize("pad", [0, 4], ids=["vec", "scalar"])
+@pytest.mark.parametrize("case", ["c64_mask", "c128_mask"])
+def test_conv_dgrad_relu_mask_passes_under_nan(case, pad):
+    """act 3 is torch's threshold_backward: the gradient is zeroed where aux <= 0 and passes everywhere else, under a
+    NaN activation too (not `aux > 0 ? v : 0`). The data of test_conv_dgrad_relu_mask_exact with NaNs planted in aux.
+    pad: the output's row stride is cin + pad -- cin takes the 8-wide epilogue, cin + 4 the per-element one (act1)."""
+    K = _k()
+    B, H, W, cout, cin = {"c64_mask": (2, 6, 10, 64, 64), "c128_mask": (1, 5, 7, 128, 64)}[case]
+    dy, w, flat = _int_conv(B, H, W, cout, cin, 51)
+    ref = flat(F.conv2d(dy, w, padding=1))
+    wpk = w.permute(0, 2, 3, 1).reshape(cin, 9 * cout)
+    a = GM.ints((B * H * W, cin), 53).to(BF)
+    a.view(-1)[::7] = float("nan")
+    ref = torch.where(a.double() <= 0, torch.zeros_like(ref), ref)
+    planted = torch.isnan(a)
+    assert (ref[planted] != 0).any() and not torch.isnan(ref).any()
+    aux = GM.place(a, cin + 8, DEV)
+    dg, wg = GM.place(flat(dy), cout, DEV), GM.place(wpk, 9 * cout, DEV)
+    out = GM.Guarded(B * H * W, cin, cin + pad, BF, DEV)
+    K.conv_fwd(dg.view, B, H, W, cout, cout, wg.view, cin, 3, 3, 1, 1, out.view, cin + pad, act=3, aux=aux.view)
+    torch.cuda.synchronize()
+    assert torch.equal(out.view.cpu(), GM.to_c(ref, BF))
+    assert out.outside_untouched()
