@@ -379,6 +379,52 @@ int sdmi_latent_noise_bwd(const void* dzin, int ld_dzin, const float* w_post, co
                           float* r, sdmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Learned-step-size (LSQ) quantisers of the quantise-and-noise layers (cim_layers/quant_noise_utils.py:101-120,
+ * layers_utils_lsq.py:31-83; sdmi/layers_qn_lsq.py). fp32, every operation rounded on its own (fl()), nothing contracted.
+ * A step is a device scalar `step` with its gradient scale g = fp32(1 / sqrt(Qp numel)), Qp = 2^(bit-1) - 1 in 1 .. 255:
+ *     se = fl(fl(s - fl(s g)) + fl(s g))           (a NULL step where one is optional: se = 1)
+ *     v = fl(x / se), c = clamp(v, -Qp, Qp) (a NaN passes), q = rint(c) (ties to even; a zero result is +0, as
+ *     round_pass's (round(c) - c) + c gives), y = fl(q se)
+ *     dx = fl((inside ? fl(dy se) : 0) / se), inside = -Qp <= v <= Qp (a NaN v is outside)
+ *     ds = fl(S g), S = sum t_i, t_i = fl(dy_i fl(q_i - v_i)) inside, fl(dy_i q_i) outside
+ * S: a thread adds its terms in the order it meets them, then a butterfly over the wave, the four waves in order, one
+ * partial per workgroup in ws (sdmi_lsq_workspace() bytes); a one-workgroup finisher adds the partials the same way.
+ * No atomics: a second call repeats every bit. No launch argument depends on a step's value. Flat tensors: n < 2^31.
+ *  sdmi_lsq_quant_fwd: y[i] and / or codes[i] = q (either may be NULL) of a flat tensor. 1 launch.
+ *  sdmi_lsq_quant_bwd: dx and ds[0] of a flat tensor; with scale_step the incoming gradient is first fl(se_scale dy[i])
+ *                      (the other GEMM operand's step). 2 launches.
+ *  sdmi_lsq_in_fwd   : x fp32 (B, C, P) -> the codes q as NHWC bf16 [B*P][ld], columns >= C zero; ld % 8 == 0, codes
+ *                      16-byte aligned. 1 launch.
+ *  sdmi_lsq_in_bwd   : as quant_bwd with dy[b][c][p] = G[(b P + p) ld + c] (the data-gradient GEMM's fp32 NHWC result),
+ *                      dx written (B, C, P). 2 launches.
+ *  sdmi_lsq_out_fwd  : over the GEMM's fp32 NHWC accumulator acc [B*P][ld]: pre = fl(fl(acc fl(se_in se_w)) + bias[c])
+ *                      (bias may be NULL) replaces acc for c < C (have_pre != 0: acc already holds pre and is left);
+ *                      y (B, C, P) = the quantiser's y of pre, or pre when qp == 0. 1 launch.
+ *  sdmi_lsq_out_bwd  : dy fp32 (B, C, P), pre as above -> d_pre = dx as NHWC bf16 [B*P][ld_d] (RNE, columns >= C zero;
+ *                      ld_d % 8 == 0, 16-byte aligned) and ds[0]. 2 launches.
+ *  sdmi_lsq_scale    : out[i] = fl(x[i] se), or fl(x[i] / se) when divide != 0. 1 launch.
+ *  sdmi_lsq_init_step: range = max |x| (NaN if any element is); step[0] = fl(1 / fl(fl(1 / range) Qp)); range == 0
+ *                      leaves step[0] as it is. 2 launches.
+ * ------------------------------------------------------------------------------------------- */
+size_t sdmi_lsq_workspace(void);
+int sdmi_lsq_quant_fwd(const float* x, long long n, const float* step, float g, int qp, float* y, float* codes,
+                       sdmi_stream_t stream);
+int sdmi_lsq_quant_bwd(const float* x, const float* dy, long long n, const float* step, float g, int qp,
+                       const float* scale_step, float scale_g, float* dx, float* ws, float* ds, sdmi_stream_t stream);
+int sdmi_lsq_in_fwd(const float* x, int B, int C, int P, const float* step, float g, int qp, void* codes, int ld,
+                    sdmi_stream_t stream);
+int sdmi_lsq_in_bwd(const float* x, const float* G, int ld, int B, int C, int P, const float* step, float g, int qp,
+                    const float* scale_step, float scale_g, float* dx, float* ws, float* ds, sdmi_stream_t stream);
+int sdmi_lsq_out_fwd(float* acc, int ld, int B, int C, int P, const float* step_in, float g_in, const float* step_w,
+                     float g_w, const float* bias, const float* step_out, float g_out, int qp, int have_pre, float* y,
+                     sdmi_stream_t stream);
+int sdmi_lsq_out_bwd(const float* pre, int ld, const float* dy, int B, int C, int P, const float* step, float g, int qp,
+                     void* dpre, int ld_d, float* ws, float* ds, sdmi_stream_t stream);
+int sdmi_lsq_scale(const float* x, long long n, const float* step, float g, int divide, float* out,
+                   sdmi_stream_t stream);
+int sdmi_lsq_init_step(const float* x, long long n, int qp, float* ws, float* step, sdmi_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Latent interface of the KL autoencoder (models/vae.py:96-100) and its closed-form KL term:
  *     moments = pre_quant_conv(h), mean = moments[:, :z], logvar = moments[:, z:], sample = mean + exp(0.5 logvar) eps,
  *     KL = (1 / B) sum_b 0.5 sum_{c,h,w} (exp(logvar) + mean^2 - 1 - logvar).

@@ -154,6 +154,15 @@ SIGNATURES = {
     "sdmi_latent_range": ([_P, _L, _P, _P], _I),
     "sdmi_latent_noise_fwd": ([_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _I, _P, _I, _P], _I),
     "sdmi_latent_noise_bwd": ([_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P], _I),
+    "sdmi_lsq_workspace": ([], _SZ),
+    "sdmi_lsq_quant_fwd": ([_P, _L, _P, _F, _I, _P, _P, _P], _I),
+    "sdmi_lsq_quant_bwd": ([_P, _P, _L, _P, _F, _I, _P, _F, _P, _P, _P, _P], _I),
+    "sdmi_lsq_in_fwd": ([_P, _I, _I, _I, _P, _F, _I, _P, _I, _P], _I),
+    "sdmi_lsq_in_bwd": ([_P, _P, _I, _I, _I, _I, _P, _F, _I, _P, _F, _P, _P, _P, _P], _I),
+    "sdmi_lsq_out_fwd": ([_P, _I, _I, _I, _I, _P, _F, _P, _F, _P, _P, _F, _I, _I, _P, _P], _I),
+    "sdmi_lsq_out_bwd": ([_P, _I, _P, _I, _I, _I, _P, _F, _I, _P, _I, _P, _P, _P], _I),
+    "sdmi_lsq_scale": ([_P, _L, _P, _F, _I, _P, _P], _I),
+    "sdmi_lsq_init_step": ([_P, _L, _I, _P, _P, _P], _I),
     "sdmi_kl_workspace": ([_L], _SZ),
     "sdmi_kl_bwd_workspace": ([], _SZ),
     "sdmi_kl_sample": ([_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P], _I),

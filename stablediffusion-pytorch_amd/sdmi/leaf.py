@@ -83,6 +83,13 @@ def _packed(mod, w, build):
     return ent["pk"]
 
 
+def invalidate_pack(key):
+    """Drop the cached pack state of one cache key (a module, or another object handed to _packed)."""
+    ent = _PACKS.get(key)
+    if ent is not None:
+        ent["ver"] = None
+
+
 def invalidate_packs(mod=None):
     """Drop the cached pack state of `mod`'s leaves (every leaf when mod is None): the next forward repacks."""
     if mod is None:
@@ -176,7 +183,8 @@ class _Conv2d(torch.autograd.Function):
         return None, dx, dw, db
 
 
-def conv2d(mod, x):
+def check_conv_geometry(mod, x):
+    """Raise unless (mod, x) is a convolution the implicit-GEMM kernels run: 'same' stride 1, or k4 s2 p1."""
     s, p = mod.stride, mod.padding
     ok = (mod.groups == 1 and tuple(mod.dilation) == (1, 1) and s[0] == s[1] and p[0] == p[1]
           and mod.padding_mode == "zeros" and not isinstance(p, str) and x.dim() == 4
@@ -184,6 +192,10 @@ def conv2d(mod, x):
                or (s[0], p[0], tuple(mod.kernel_size)) == (2, 1, (4, 4))))
     if not ok:
         raise NotImplementedError(f"HIP leaf Conv2d: unsupported geometry {mod}")
+
+
+def conv2d(mod, x):
+    check_conv_geometry(mod, x)
     return _Conv2d.apply(mod, x, mod.weight, mod.bias)
 
 
