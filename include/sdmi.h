@@ -425,6 +425,51 @@ int sdmi_lsq_scale(const float* x, long long n, const float* step, float g, int 
 int sdmi_lsq_init_step(const float* x, long long n, int qp, float* ws, float* step, sdmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * ADC/DAC-aware compute-in-memory layers (cim_layers/layers_qn_lsq_adda_cim.py, layers_utils_adda.py;
+ * sdmi/layers_qn_lsq_adda_cim.py; arithmetic and layouts at the top of csrc/adda.hip).
+ * M = B P rows, K input channels in nb = ceil(K / rb) row blocks (rb is clipped to K), N output columns,
+ * sb = dac_bit - 1, L = ceil((input_bit - 1) / sb) slices, R = 2^(adc_bit-1) - 1. Padded sizes: rbp = 32 ceil(rb / 32),
+ * Kp = nb rbp, Mp = 64 ceil(M / 64), Np = 64 ceil(N / 64). The steps and adc_scale are device scalars; step_w / step_in
+ * are the raw steps (NULL: factor 1). No atomics: a second call repeats every bit.
+ *  sdmi_adda_geometry    : out[0..5] = nb, rbp, L, Mp, Np, Kp (host only).
+ *  sdmi_adda_in_fwd      : x fp32 (B, C, P) -> the L slices of its LSQ codes, bf16 [L][Mp][Kp], pads zero. 1 launch.
+ *  sdmi_adda_pack_w      : w fp32 [N][K] -> hi = bf16(w) [Np][Kp] and, when lo is not NULL, lo = bf16(w - hi). 1 launch.
+ *  sdmi_adda_gemm        : the segmented, bit-sliced product: per (row block, slice) the partial sum is scaled by
+ *                          adc_scale, noised (gain_noise / offset_noise, both or neither, N <= 1000), clamped to
+ *                          [-R-1, R] and rounded, then summed with weight 2^(i sb); pre fp32 [M][ld] =
+ *                          fl(fl(fl(fl(Z / ws) / is) / as) + bias). mask (ceil(nb L / 32) words [M][ld] each, bit j L + i:
+ *                          the ADC input was inside the range) and T (fp32 [M][ld], the sum of the unsaturated partial
+ *                          sums with the same weights) are written when not NULL, together or not at all. 1 launch.
+ *  sdmi_adda_bwd_ops     : d_pre bf16 [M][ld_d] and the mask -> U bf16 [nb][M][ld_d] (dZ times the count of unsaturated
+ *                          slices of the block), V bf16 [nb][L Mp][ld_d] (2^(i sb) dZ where slice i of the block was
+ *                          unsaturated, pad rows zero) and dscale[0] = the gradient of adc_scale (dscale[1], [2]: its two
+ *                          sums); ws of sdmi_adda_workspace() bytes. 2 launches.
+ *  sdmi_adda_in_bwd      : sdmi_lsq_in_bwd on G fp32 [B P][Kp] (block-padded columns) with the incoming gradient
+ *                          fl(fl(G fl(as / L)) / se); ws of sdmi_lsq_workspace() bytes. 2 launches.
+ *  sdmi_adda_unpack_wgrad: out fp32 [N][K] = fl(as G2[n][padded k]), G2 fp32 [>= N][Kp]. 1 launch.
+ *  sdmi_adda_absmax      : out[0] = max |x| (NaN if any element is); ws of sdmi_lsq_workspace() bytes. 2 launches.
+ * ------------------------------------------------------------------------------------------- */
+size_t sdmi_adda_workspace(void);
+int sdmi_adda_geometry(int M, int N, int K, int rb, int input_bit, int dac_bit, int* out);
+int sdmi_adda_in_fwd(const float* x, int B, int C, int P, const float* step, float g, int input_bit, int dac_bit, int rb,
+                     void* slices, sdmi_stream_t stream);
+int sdmi_adda_pack_w(const float* w, int N, int K, int rb, void* hi, void* lo, sdmi_stream_t stream);
+int sdmi_adda_gemm(const void* slices, const void* w_hi, const void* w_lo, int M, int N, int K, int rb, int input_bit,
+                   int dac_bit, int adc_bit, const float* adc_scale, const float* gain_noise, const float* offset_noise,
+                   const float* step_w, const float* step_in, const float* bias, float* pre, int ld, unsigned* mask,
+                   float* T, sdmi_stream_t stream);
+int sdmi_adda_bwd_ops(const void* dpre, int ld_d, const float* pre, int ld, const float* bias, const float* T,
+                      const unsigned* mask, int M, int N, int nb, int L, int sb, const float* adc_scale,
+                      const float* step_w, const float* step_in, void* U, void* V, float* ws, float* dscale,
+                      sdmi_stream_t stream);
+int sdmi_adda_in_bwd(const float* x, const float* G, int B, int C, int P, int rb, const float* step, float g,
+                     int input_bit, int dac_bit, const float* adc_scale, float* dx, float* ws, float* ds,
+                     sdmi_stream_t stream);
+int sdmi_adda_unpack_wgrad(const float* G2, int N, int K, int rb, const float* adc_scale, float* out,
+                           sdmi_stream_t stream);
+int sdmi_adda_absmax(const float* x, long long n, float* ws, float* out, sdmi_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Latent interface of the KL autoencoder (models/vae.py:96-100) and its closed-form KL term:
  *     moments = pre_quant_conv(h), mean = moments[:, :z], logvar = moments[:, z:], sample = mean + exp(0.5 logvar) eps,
  *     KL = (1 / B) sum_b 0.5 sum_{c,h,w} (exp(logvar) + mean^2 - 1 - logvar).

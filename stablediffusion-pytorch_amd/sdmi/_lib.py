@@ -163,6 +163,15 @@ SIGNATURES = {
     "sdmi_lsq_out_bwd": ([_P, _I, _P, _I, _I, _I, _P, _F, _I, _P, _I, _P, _P, _P], _I),
     "sdmi_lsq_scale": ([_P, _L, _P, _F, _I, _P, _P], _I),
     "sdmi_lsq_init_step": ([_P, _L, _I, _P, _P, _P], _I),
+    "sdmi_adda_workspace": ([], _SZ),
+    "sdmi_adda_geometry": ([_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int)], _I),
+    "sdmi_adda_in_fwd": ([_P, _I, _I, _I, _P, _F, _I, _I, _I, _P, _P], _I),
+    "sdmi_adda_pack_w": ([_P, _I, _I, _I, _P, _P, _P], _I),
+    "sdmi_adda_gemm": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P], _I),
+    "sdmi_adda_bwd_ops": ([_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "sdmi_adda_in_bwd": ([_P, _P, _I, _I, _I, _I, _P, _F, _I, _I, _P, _P, _P, _P, _P], _I),
+    "sdmi_adda_unpack_wgrad": ([_P, _I, _I, _I, _P, _P, _P], _I),
+    "sdmi_adda_absmax": ([_P, _L, _P, _P, _P], _I),
     "sdmi_kl_workspace": ([_L], _SZ),
     "sdmi_kl_bwd_workspace": ([], _SZ),
     "sdmi_kl_sample": ([_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P], _I),
