@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from sdmi import _lib
+from sdmi.module_glue import TAPE_FREED
 from sdmi.lpips_engine import CHANNELS, SLICES, LPIPSEngine
 
 _CPU_ERROR = "the sdmi LPIPS runs on the MI355X HIP path only (move the model and inputs to cuda)"
@@ -88,6 +89,8 @@ class LPIPSFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dval):
+        if ctx.c is None:
+            raise RuntimeError(TAPE_FREED)
         g0, g1 = ctx.eng.backward(ctx.c, dval.float().contiguous(), want=ctx.need)
         ctx.c = None
         return None, None, g0, g1

@@ -22,6 +22,7 @@ from models.blocks import DownBlock, MidBlock, UpBlock
 from sdmi import _lib
 from sdmi import kernels as K
 from sdmi import leaf as LF
+from sdmi.module_glue import NO_INPUT_GRAD, check_tape
 from sdmi.vae_engine import VAEEngine
 from sdmi.vae_train import VAETrainEngine
 
@@ -58,15 +59,18 @@ class VAEFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mod, eps, x, *params):
+        if ctx.needs_input_grad[2]:
+            raise RuntimeError(NO_INPUT_GRAD)
         eng = mod._train_eng(x)
         B, C, H, W = x.shape
         out, c = eng.forward(x, eps=eps)
-        ctx.mod, ctx.c, ctx.hw = mod, c, (B, H, W)
+        ctx.mod, ctx.c, ctx.hw, ctx.packs_of = mod, c, (B, H, W), mod._packs_of
         return eng.pred_to_nchw(out, B, H, W), c["moments"]
 
     @staticmethod
     def backward(ctx, dimg, dmom):
         mod = ctx.mod
+        check_tape(ctx.c, ctx.packs_of, mod._packs_of)
         eng = mod._tengine
         B, H, W = ctx.hw
         dout = (eng.dpred_from_nchw(dimg.float().contiguous()) if dimg is not None
@@ -157,6 +161,8 @@ class VAE(nn.Module):
                                            im_channels=self.im_channels)
             self._tptrs = ptrs
         self._tengine.refresh_weights()
+        # what a later backward checks its own forward's record against (`.data` writes keep the versions)
+        self._packs_of = (self._tengine, tuple(p._version for p in params.values()))
         return self._tengine
 
     def _leaf(self):
@@ -210,6 +216,8 @@ class VAE(nn.Module):
         if self._leaf():
             z, encoder_output = self._leaf_encode(x)
             return self._leaf_decode(z), encoder_output
+        if torch.is_grad_enabled() and x.requires_grad:  # (before anything is packed or drawn)
+            raise RuntimeError(NO_INPUT_GRAD)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             self._train_eng(x)  # (raises off the HIP path before anything is drawn)
             return VAEFunction.apply(self, self._draw(x), x, *self.parameters())

@@ -18,6 +18,7 @@ import torch.nn as nn
 from models.blocks import DownBlock, MidBlock, UpBlock
 from sdmi import _lib
 from sdmi import leaf as LF
+from sdmi.module_glue import NO_INPUT_GRAD, check_tape
 from sdmi.vqvae_engine import VQVAEEngine
 from sdmi.vqvae_train import VQVAETrainEngine
 
@@ -27,16 +28,19 @@ class VQVAEFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mod, x, *params):
+        if ctx.needs_input_grad[1]:
+            raise RuntimeError(NO_INPUT_GRAD)
         eng = mod._train_eng(x)
         B, C, H, W = x.shape
         out, c = eng.forward(x)
-        ctx.mod, ctx.c, ctx.hw = mod, c, (B, H, W)
+        ctx.mod, ctx.c, ctx.hw, ctx.packs_of = mod, c, (B, H, W), mod._packs_of
         vq = c["vq_loss"].reshape(())
         return eng.pred_to_nchw(out, B, H, W), c["zq"], vq.clone(), vq.clone()
 
     @staticmethod
     def backward(ctx, dimg, dz, dcb, dcm):
         mod = ctx.mod
+        check_tape(ctx.c, ctx.packs_of, mod._packs_of)
         eng = mod._tengine
         B, H, W = ctx.hw
         dev = eng.device
@@ -133,6 +137,7 @@ class VQVAE(nn.Module):
         if torch.is_grad_enabled() or sig != self._tsig:
             self._tengine.refresh_weights()
             self._tsig = sig
+            self._packs_of = (self._tengine, sig)  # what a later backward checks its own forward's record against
         return self._tengine
 
     def model_config_dict(self):
@@ -195,6 +200,8 @@ class VQVAE(nn.Module):
         if self._leaf():
             z, losses, _ = self._leaf_encode(x)
             return self._leaf_decode(z), z, losses
+        if torch.is_grad_enabled() and x.requires_grad:  # (before the weights are packed: nothing has been launched)
+            raise RuntimeError(NO_INPUT_GRAD)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             out, z, cb, cm = VQVAEFunction.apply(self, x, *self.parameters())
             return out, z, {"codebook_loss": cb, "commitment_loss": cm}

@@ -23,6 +23,7 @@ from models.vqvae import VQVAEFunction
 from sdmi import _lib
 from sdmi import kernels as K
 from sdmi import leaf as LF
+from sdmi.module_glue import NO_INPUT_GRAD
 
 
 def _scale(n_scale):
@@ -68,10 +69,12 @@ class VQVAENoiseFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mod, n_scale, eps, x, *params):
+        if ctx.needs_input_grad[3]:
+            raise RuntimeError(NO_INPUT_GRAD)
         eng = mod._train_eng(x)
         B, C, H, W = x.shape
         out, c = eng.forward(x, n_scale=n_scale, eps=eps)
-        ctx.mod, ctx.c, ctx.hw = mod, c, (B, H, W)
+        ctx.mod, ctx.c, ctx.hw, ctx.packs_of = mod, c, (B, H, W), mod._packs_of
         vq = c["vq_loss"].reshape(())
         return eng.pred_to_nchw(out, B, H, W), c["z"], vq.clone(), vq.clone()
 
@@ -107,6 +110,8 @@ class VQVAE(_CleanVQVAE):
             z, losses = self.encode(x, n_scale)
             return self._leaf_decode(z), z, losses
         ns = _scale(n_scale)
+        if torch.is_grad_enabled() and x.requires_grad:  # (before anything is packed or drawn)
+            raise RuntimeError(NO_INPUT_GRAD)
         training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if ns == 0 and training:
             return super().forward(x)  # models.vqvae's autograd Function: nothing is drawn

@@ -9,7 +9,12 @@ Two backward forms (same kernels, same gradients):
   DistributedDataParallel (train_ddpm_cond_celebhq_multi_gpu.py:257-263) and relies on its per-parameter autograd
   hooks to start bucket all-reduces during the backward (:362); with a single node every hook fires at the end and
   nothing overlaps. Used when torch.distributed is initialised with world size > 1 (module attribute
-  `sdmi_staged_backward` = True / False overrides)."""
+  `sdmi_staged_backward` = True / False overrides).
+
+What a caller may do with these nodes beyond one forward, one backward, zero_grad(set_to_none=True) -- several forwards
+per graph, kept gradients, accumulation, frozen subsets -- and what raises instead of going wrong silently (an input
+that requires grad, a backward on packs a later forward replaced, a second backward through one forward) is DESIGN.md's
+"supported autograd surface", held by tests/test_autograd_contract_gpu.py."""
 import torch
 import torch.distributed as dist
 
@@ -25,6 +30,32 @@ def _require_gpu(t):
     _lib.lib()  # fail loudly when the extension is missing
 
 
+NO_INPUT_GRAD = ("the fused engine computes no input gradient: the image input requires grad, and the whole-network "
+                 "engine returns parameter gradients only; set `sdmi_leaf_path = True` on the module to run the leaf "
+                 "path, which does (or detach the input)")
+TAPE_FREED = ("the tape is freed after the first backward: this forward's saved activations are gone, so a second "
+              "backward through it (retain_graph=True) cannot run; call the module again")
+STALE_PACKS = ("backward after a later forward repacked updated weights: the parameters changed in place between this "
+               "forward and a later forward of the same module, whose bf16 weight packs the engine now holds; run each "
+               "backward before the optimizer step that precedes the next forward")
+
+
+def same_packs(at_forward, now):
+    """A backward multiplies by the engine's current bf16 weight packs, so they must still be its own forward's. Both
+    arguments are (engine, parameter `_version`s) as recorded when the packs were made. Host-side, before any launch.
+    Updates written through `.data` keep the version counters and stay undetected."""
+    if at_forward is None or now is None or at_forward[0] is not now[0] or at_forward[1] != now[1]:
+        raise RuntimeError(STALE_PACKS)
+
+
+def check_tape(tape, at_forward, now):
+    """The two host-side checks of a fused backward, before it launches anything: the tape is still there (a first
+    backward frees it) and the packs are still its forward's."""
+    if tape is None:
+        raise RuntimeError(TAPE_FREED)
+    same_packs(at_forward, now)
+
+
 class EngineHolder:
     """Per-module state: flat store the nn.Parameters live in, and the engine bound to it.
     base: "cond" / "uncond" (UNet) or "dit"."""
@@ -36,7 +67,11 @@ class EngineHolder:
         self.store = None
         self.engine = None
         self._packed_sig = None
+        self._packs_of = None  # (engine, parameter versions) the bf16 packs were last made from
         self._gflat = None
+        self._gstorage = None
+        self.last_run = None  # the latest staged forward's run (its `handed` count: test / overlap evidence)
+        self._open_run = None  # a staged backward that has begun and not finished
         self._stages = {}  # tape-label signature -> segment plan of the staged backward
 
     def ensure(self, device):
@@ -72,6 +107,10 @@ class EngineHolder:
         if torch.is_grad_enabled() or sig != self._packed_sig:
             self.engine.refresh_weights()
             self._packed_sig = sig
+            self._packs_of = (self.engine, sig)
+
+    def check_packs(self, packs_of):
+        same_packs(packs_of, self._packs_of)
 
     def invalidate(self):
         """Force a repack at the next forward (weights changed behind the version counter, e.g. via `.data`)."""
@@ -79,18 +118,30 @@ class EngineHolder:
 
     def grad_buffer(self, device):
         """The flat fp32 buffer a backward writes every parameter gradient into (store order), reused across
-        backwards (verdict r5: a fresh 474 MB buffer per backward at the full cond-UNet). autograd hands the per-
-        parameter views to `.grad` without a copy when `.grad` is None (zero_grad(set_to_none=True), the reference's
-        loops), so a `.grad` that still aliases the buffer -- gradient accumulation without zeroing, where the next
-        backward is ADDED into `.grad` -- gets a fresh buffer instead of being overwritten."""
+        backwards (verdict r5: a fresh 474 MB buffer per backward at the full cond-UNet) -- but only while nothing else
+        can still read it. A backward hands autograd views of it, and they live on in many places: `.grad` (autograd
+        takes a view over without a copy when `.grad` is None), autograd's input buffers while a second forward of the
+        same graph has yet to run its backward, the tuple torch.autograd.grad returned, a `.grad` the caller kept. All
+        of them share the buffer's storage, so the buffer is free exactly when its storage has no user but the holder
+        (the buffer and the storage object kept beside it); otherwise the backward gets a fresh one and the old one
+        stays with whoever reads it. On the reference's loop (zero_grad(set_to_none=True), forward, backward, step) the
+        buffer is free at every backward: one allocation for the whole run (tests/test_autograd_contract_gpu.py, C4;
+        a torch without the use-count entry point never reuses, which that test reports)."""
         g = self._gflat
-        if g is not None and g.device == torch.device(device):
-            sp = g.untyped_storage().data_ptr()
-            if not any(p.grad is not None and p.grad.device == g.device and p.grad.untyped_storage().data_ptr() == sp
-                       for p in self.module.parameters()):
-                return g
+        users = getattr(torch._C, "_storage_Use_Count", None)
+        if g is not None and users is not None and g.device == torch.device(device) \
+                and g.numel() == self.store.numel and users(self._gstorage._cdata) == 2:
+            return g
         self._gflat = torch.empty(self.store.numel, dtype=torch.float32, device=device)
+        self._gstorage = self._gflat.untyped_storage()
         return self._gflat
+
+    def release_views(self):
+        """The engine's own references to the last backward's gradient views (they would keep the buffer in use)."""
+        eng = self.engine
+        eng.Gd = None
+        if getattr(eng, "temb_grad_all", None) is not None:
+            eng.temb_grad_all = None
 
 
 def invalidate_module(module):
@@ -118,17 +169,23 @@ def engine_path_ok(model):
 class DenoiserFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, holder, x, t, text, mask, klass, *params):
+        if ctx.needs_input_grad[1]:
+            raise RuntimeError(NO_INPUT_GRAD)
         eng = holder.engine
         B, C, H, W = x.shape
         pred, tape = eng.forward(x, t, text, mask, need_backward=True, klass=klass)
         out = eng.pred_to_nchw(pred, B, H, W)
         ctx.holder = holder
         ctx.tape = tape
+        ctx.packs_of = holder._packs_of
         return out
 
     @staticmethod
     def backward(ctx, dout):
         holder = ctx.holder
+        if ctx.tape is None:
+            raise RuntimeError(TAPE_FREED)
+        holder.check_packs(ctx.packs_of)
         eng = holder.engine
         store = holder.store
         dpred = eng.dpred_from_nchw(dout.float().contiguous())
@@ -136,8 +193,10 @@ class DenoiserFunction(torch.autograd.Function):
         gviews = {k: store.view(gflat, k) for k in store.order}
         eng.backward(ctx.tape, dpred, grads=gviews)
         ctx.tape = None
+        holder.release_views()
         names = [k for k, _ in holder.module.named_parameters()]
-        return (None, None, None, None, None, None) + tuple(gviews[k] for k in names)
+        # (popped, not indexed: the returned views are then autograd's alone, and it takes them over without a copy)
+        return (None, None, None, None, None, None) + tuple(gviews.pop(k) for k in names)
 
 
 UNetFunction = DenoiserFunction
@@ -196,6 +255,8 @@ class _StagedRun:
     def __init__(self, holder, tape_ctx, shape, segs, tail):
         self.holder, self.ctx, self.shape = holder, tape_ctx, shape
         self.segs, self.tail = segs, tail
+        self.packs_of = holder._packs_of
+        self.gviews = None
         self.gen = None
         self.tok = None
         self.events = []
@@ -203,11 +264,26 @@ class _StagedRun:
 
     def begin(self, dout):
         h = self.holder
+        if self.ctx is None:
+            raise RuntimeError(TAPE_FREED)
+        h.check_packs(self.packs_of)
+        prev, h._open_run = h._open_run, self
+        if prev is not None and prev.gen is not None:
+            # torch.autograd.grad over some of the parameters runs only the nodes that lead to them: a run whose last
+            # node was pruned is finished here (the engine's flush and join), its remaining gradients unread
+            prev.last()
         eng, store = h.engine, h.store
         dpred = eng.dpred_from_nchw(dout.float().contiguous())
         gflat = h.grad_buffer(dout.device)
         self.gviews = {k: store.view(gflat, k) for k in store.order}
         self.gen = eng.backward_steps(self.ctx, dpred, grads=self.gviews)
+        self.tok, self.events, self.handed = None, [], 0
+
+    def _hand(self, keys):
+        """The views of `keys`, taken out of gviews: once returned they are autograd's alone (it takes a gradient over
+        without a copy only when nobody else holds it, and the holder's buffer counts as free only when no view of it
+        is left)."""
+        return tuple(self.gviews.pop(k) for k in keys)
 
     def _advance(self, stop):
         """Run the engine backward until it has yielded a token <= stop (tokens decrease; the DiT engine yields only
@@ -240,16 +316,22 @@ class _StagedRun:
         for ev in self.events[j - 1]:
             plan.wait_event(cur, ev)
         self.handed += 1
-        return tuple(self.gviews[k] for k in self.segs[j - 1][1])
+        return self._hand(self.segs[j - 1][1])
 
     def last(self):
-        """Exhaust the engine backward (its own join of every side stream) and return the rest."""
+        """Exhaust the engine backward (its own join of every side stream), return the rest and let go of the forward
+        tape, the prediction and the views: `handed` alone outlives the backward."""
         for _ in self.gen:
             pass
         keys = (self.segs[-1][1] if self.segs else []) + self.tail
         self.handed += 1
-        self.gen = None
-        return tuple(self.gviews[k] for k in keys)
+        out = self._hand(keys)
+        self.gen = self.ctx = self.shape = self.gviews = None
+        self.events = []
+        self.holder.release_views()
+        if self.holder._open_run is self:
+            self.holder._open_run = None
+        return out
 
 
 class _StageOut(torch.autograd.Function):
@@ -289,13 +371,13 @@ class _StageFirst(torch.autograd.Function):
     """First node of the forward chain (its backward runs last): finishes the engine backward."""
 
     @staticmethod
-    def forward(ctx, run, *params):
+    def forward(ctx, run, anchor, *params):
         ctx.run = run
-        return params[0].new_zeros(0) if params else torch.zeros(0, device="cuda")
+        return anchor.new_zeros(0)
 
     @staticmethod
     def backward(ctx, dh):
-        return (None,) + ctx.run.last()
+        return (None, None) + ctx.run.last()
 
 
 def staged_apply(holder, pred, tape_ctx, B, H, W):
@@ -308,9 +390,12 @@ def staged_apply(holder, pred, tape_ctx, B, H, W):
     segs, tail = holder._stages[sig]
     named = dict(holder.module.named_parameters())
     run = _StagedRun(holder, tape_ctx, (B, H, W, pred), segs, tail)
-    # forward chain: first node owns the gradients handed out last
+    # forward chain: first node owns the gradients handed out last. The chain hangs on an anchor that requires grad, so
+    # every node runs in a backward whichever parameters are frozen (a node none of whose inputs required grad would
+    # be skipped, and with it a segment of the engine backward)
     keys_last = (segs[-1][1] if segs else []) + tail
-    h = _StageFirst.apply(run, *[named[k] for k in keys_last])
+    anchor = torch.zeros(0, device=pred.device, requires_grad=True)
+    h = _StageFirst.apply(run, anchor, *[named[k] for k in keys_last])
     for j in range(len(segs) - 1, 0, -1):
         h = _Stage.apply(run, j, h, *[named[k] for k in segs[j - 1][1]])
     out = _StageOut.apply(run, h)
@@ -327,10 +412,12 @@ def staged_enabled(module):
 
 def run_unet(module, holder, x, t, text=None, mask=None, klass=None):
     _require_gpu(x)
+    if torch.is_grad_enabled() and x.requires_grad:  # (before the weights are packed: nothing has been launched)
+        raise RuntimeError(NO_INPUT_GRAD)
     eng = holder.ensure(x.device)
     params = [p for _, p in module.named_parameters()]
     holder.refresh(params)
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
         if staged_enabled(module):
             B, C, H, W = x.shape
             pred, tape_ctx = eng.forward(x, t, text, mask, need_backward=True, klass=klass)
